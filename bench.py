@@ -9,13 +9,22 @@ excluded); a timed pass is what geoac_fan_run does: launch angles h
 post-pass, sums), arrival records device -> host - and for N > 1 the RCCL gather of the arrival tables in between.
 `launch_only` repeats the figure without the two copies (HIP events around the kernels).
 
-Parity gate before timing: the warm-up pass's records are compared with tests/golden/full_metric.npz, the fan as the COMPILED
+A plain run (`--gpus 1 --steps N --warmup W`) does only what the line's headline figure needs: set-up, W untimed passes, N timed
+passes, the outputs if --dump-outputs is given, the JSON line (metric, value, unit, ms_per_step, dtype, config).  Everything else
+below - the parity gate, launch_only, roofline, other_scalings and cpu_baseline - runs with --full.
+
+--dump-outputs DIR: after the timed passes, the arrays the last timed pass returned to its caller, as DIR/<name>.npy (float64):
+records.npy = the arrival record table [rays][legs][32] of the whole fan (N > 1: rank 0's gathered table; above 64 MB a fixed
+seeded sample of rays, whose indices go to records_ray_index.npy), ray_steps.npy = [RK4 ray-steps of the pass, all ranks].
+The inputs are fixed by the arguments, so two builds of the project can be compared output for output.
+
+Parity gate before timing (--full): the warm-up pass's records are compared with tests/golden/full_metric.npz, the fan as the COMPILED
 REFERENCE integrated it (tests/golden/make_golden_full.py): step count and outcome of every (ray, leg) exact, travel time /
 attenuation / turning height / arrival angles / amplitude / range within 1e-6.  A failed gate aborts the bench.
 
 N > 1 (one process per GPU, torch.distributed/RCCL).  `--scaling weak` (default; the line's `value`): the fan has N x 360 azimuths
 (phi step 1/N degree), rank r integrates azimuth indices r, r+N, ... - per-GPU work fixed.  `--scaling strong`: the metric fan itself,
-360 azimuths dealt round-robin to the ranks.  Whatever the line is, the other flavour and the strong-scaling run of BASELINE's
+360 azimuths dealt round-robin to the ranks.  With --full, whatever the line is, the other flavour and the strong-scaling run of BASELINE's
 config 4 (GeoAc3D.RngDep, 5x5x1400 grid, 1000 az x 1000 incl = 1 M rays sharded by azimuth) are measured in the same run and
 reported under "other_scalings" (skip with --no-extras).  Arrival records are all-gathered over xGMI and the step counts all-reduced.
 value = all ranks' RK4 ray-steps / max-over-ranks time.
@@ -174,6 +183,8 @@ class FanRun:
         self.steps_t = torch.zeros(1, dtype=torch.int64, device=coll_dev)
         self.rec = None            # N = 1: this pass's records; N > 1, rank 0, when want_full: the whole fan's gathered table (parity gate)
         self.want_full = False
+        self.keep_last = False     # N > 1: hold on to the last pass's gathered table (device) for --dump-outputs
+        self.last_full, self.last_steps = None, 0
         self.np, self.torch = np, torch
 
     def one_pass(self):
@@ -182,6 +193,7 @@ class FanRun:
         ctx = self.ctx
         if not self.collective:
             self.rec, steps = ctx.run(self.theta, self.phi, out=self.rec_host.numpy())    # set_angles + launch + fetch (geoac_fan_run)
+            self.last_steps = steps
             return steps
         # a rank that cannot run its share (out of memory on a shared device, ...) must not leave the others waiting in the gather: every rank
         # learns about it before any data collective and all of them raise
@@ -206,7 +218,10 @@ class FanRun:
         self.torch.cuda.current_stream().synchronize()
         if self.rank == 0 and self.want_full:
             self.rec = full.cpu().numpy()
-        return int(self.steps_t.item())
+        if self.keep_last:
+            self.last_full = full
+        self.last_steps = int(self.steps_t.item())
+        return self.last_steps
 
     def timed(self, n_pass):
         """barrier + sync, n_pass passes, sync + barrier; returns (ray-steps, max-over-ranks seconds, kernel-event sums)"""
@@ -247,6 +262,28 @@ def agree(ok, collective, coll_dev, what, err=None):
         all_ok = bool(ok)
     if not all_ok:
         raise RuntimeError(f"{what}: {err!r}" if err is not None else f"{what}: failed on another rank")
+
+
+DUMP_BYTES_MAX = 64_000_000   # --dump-outputs: all files together
+
+
+def dump_outputs(dirpath, run):
+    """rank 0: the last timed pass's outputs as DIR/<name>.npy (float64) - the arrival record table its caller receives (N > 1: the gathered
+    table of the whole fan) and its ray-step count; a table above the size cap is cut to a fixed, seeded sample of rays, whose indices are
+    written beside it"""
+    import numpy as np
+    rec = np.asarray(run.last_full.cpu().numpy() if run.collective else run.rec, dtype=np.float64)
+    out = {"ray_steps": np.array([run.last_steps], dtype=np.float64)}
+    room = DUMP_BYTES_MAX - 4096                                           # headers and ray_steps.npy
+    if rec.nbytes > room:
+        keep = room // (rec[0].nbytes + 8)                                 # a sampled ray: its records and its index
+        idx = np.sort(np.random.default_rng(0).choice(len(rec), size=keep, replace=False))
+        out["records_ray_index"] = idx.astype(np.float64)
+        rec = rec[idx]
+    out["records"] = rec
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirpath, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def parity_gate(rec, phi_step_mult):
@@ -398,7 +435,7 @@ def spawn_ranks(args):
     GPU is ever replaced by another program).  The child's JSON line is relayed with this process's cpu_baseline merged in."""
     import socket
     import subprocess
-    cpu = None if args.no_cpu_baseline else cpu_baseline()
+    cpu = cpu_baseline() if args.full and not args.no_cpu_baseline else None
     if args.backend == "nccl":
         import torch
         have = torch.cuda.device_count()                   # counts devices without initialising one
@@ -430,15 +467,19 @@ def spawn_ranks(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--steps", type=int, default=3, help="timed passes")
+    ap.add_argument("--warmup", type=int, default=1, help="untimed passes before them")
+    ap.add_argument("--full", action="store_true", help="also the parity gate, launch_only, roofline, other_scalings and cpu_baseline (a plain run: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed pass's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak", help="which N > 1 fan the line's value is measured on")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other-scaling and config-4 measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other-scaling and config-4 measurements")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, the measured path) or gloo (rehearsal of the N>1 flow on fewer GPUs than ranks)")
     ap.add_argument("--force-collective", action="store_true", help="take the N > 1 path (process group, RCCL all_gather / all_reduce of device tensors) at N = 1 too: "
                     "under torch.distributed.run --nproc-per-node 1 this executes the RCCL path on a one-GPU box (tests/test_gpu_nccl.py)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ        # under torch.distributed.run (the driver's N > 1 line, or spawn_ranks' child)
     if args.gpus > 1 and not launched:
@@ -449,7 +490,7 @@ def main():
     # CPU baseline first: its worker processes are started before this process has touched the GPU (and the host cores are idle
     # again before the timed region starts).  Under a launcher rank 0 measures it while the other ranks wait for it in the rendezvous.
     cpu = None
-    if not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0:
+    if args.full and not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0:
         cpu = cpu_baseline()
 
     import numpy as np
@@ -503,9 +544,9 @@ def main():
     run, mult = metric_run(args.scaling)
     gate = {"status": "skipped", "why": "--warmup 0 (profiler passes): the gate runs on the first untimed pass"}
     for w in range(args.warmup):
-        run.want_full = (w == 0)
+        run.want_full = (w == 0) and args.full
         run.one_pass()
-        if w == 0:
+        if w == 0 and args.full:
             gerr = None
             if rank == 0:
                 try:
@@ -515,11 +556,21 @@ def main():
                     gerr = e
             agree(gerr is None, collective, coll_dev, "parity gate", gerr)  # (every rank stops, not just rank 0)
     run.want_full = False
+    run.keep_last = bool(args.dump_outputs)
     total_steps, dt, ev = run.timed(args.steps)
     local_steps_per_pass = run.ctx.total_steps()
+    if args.dump_outputs:
+        derr = None
+        if rank == 0:
+            try:
+                dump_outputs(args.dump_outputs, run)
+            except Exception as e:                                     # noqa: BLE001
+                derr = e
+        agree(derr is None, collective, coll_dev, "--dump-outputs", derr)
+    run.last_full = None
 
     extras = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             other = "strong" if args.scaling == "weak" else "weak"
             if world > 1:
@@ -575,15 +626,6 @@ def main():
 
     if rank == 0:
         value = total_steps / dt
-        rk4_ms, post_ms, rk4_launches = ev["ms_rk4"], ev["ms_post"], ev["epochs"]
-        # dominant kernel = k_rk4: algorithmic bytes per launch / average launch duration (HIP events on the kernel's own stream,
-        # recorded inside libgeoac_hip around every k_rk4 epoch of the timed passes).  One epoch of this fan is TWO concurrent k_rk4
-        # launches of the same duration by construction (the shallow tenth of the rays on k_rk4<EqGlobalPair>, the rest on
-        # k_rk4<EqGlobal<true>> with 0.75 x the rows); "launch" below = that pair, bytes and steps are those of both.
-        ach_gbs = (B_ALG_PER_STEP * local_steps_per_pass * args.steps) / (rk4_ms * 1e-3) / 1e9 if rk4_ms > 0 else 0.0
-        pmc = newest_pmc()
-        bps = pmc.get("k_rk4_hbm_bytes_per_ray_step")
-        steps_per_launch = local_steps_per_pass * args.steps / max(rk4_launches, 1)
         n_az, n_theta = run.n_az, run.n_theta
         out = {
             "metric": ("RK4 ray-steps/sec, GeoAcGlobal 360x90 ToyAtmo fan; arrivals within 1e-6 of ref" if n_az == 360 else
@@ -596,46 +638,58 @@ def main():
                        "rays_per_gpu": int(len(run.theta)), "ray_steps_per_pass": int(total_steps // args.steps),
                        "timed_region": "launch angles H2D + RK4 / post-pass / sum kernels + " + ("RCCL all_gather of the arrival tables + every rank's own arrivals D2H" if collective else "arrival records D2H (geoac_fan_run)") + "; atmosphere tables resident",
                        "parallelism": f"azimuth-sharded x{n_gpus}" + (f", {'RCCL' if args.backend == 'nccl' else args.backend} all_gather of arrivals" if collective else "")},
-            "parity_gate": gate,
-            "launch_only": {"value": local_steps_per_pass * args.steps * (n_gpus if args.scaling == "weak" else 1) / (ev["ms_total"] * 1e-3) if ev["ms_total"] > 0 and world == 1 else None,
-                            "ms_per_step": ev["ms_total"] / args.steps, "what": "HIP events around the kernels of a pass on this rank, no copies"},
-            "roofline": {"bound": "fp64_valu_latency",
-                         "bound_note": "a register-resident FP64 ODE recurrence: the pass lasts as long as the serial integration of its longest ray; "
-                                       "`achieved`/`frac` are the SURVEY 8(d) contract figure (144 B per step against HBM peak), `hbm_measured` the counter bytes, `fp64` the issue-side figure",
-                         "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": ach_gbs / HBM_PEAK_GBS,
-                         "traffic": (bps * steps_per_launch) if bps else None, "traffic_unit": "bytes per launch",
-                         "traffic_source": pmc.get("_source"), "traffic_stale": pmc.get("_stale"), "build_id": pmc.get("_build_id_now"),
-                         "traffic_note": "PMC counters (FETCH_SIZE x 2 + WRITE_SIZE, separate rocprofv3 passes of this command) cannot be collected inside the run: "
-                                         "they come from the named profile; traffic_stale = the profiled library is not the one loaded now",
-                         "achieved_bytes_per_launch": B_ALG_PER_STEP * steps_per_launch,
-                         "kernel": "k_rk4<EqGlobalPair,true,false> || k_rk4<EqGlobal<true>,true,false> (one epoch)", "launches": rk4_launches,
-                         "avg_launch_ms": rk4_ms / max(rk4_launches, 1),
-                         "alg_bytes_per_step": B_ALG_PER_STEP,
-                         "rk4_ms_per_pass": rk4_ms / args.steps, "postpass_ms_per_pass": post_ms / args.steps},
         }
-        if bps and rk4_ms > 0:
-            mg = bps * local_steps_per_pass * args.steps / (rk4_ms * 1e-3) / 1e9
-            out["roofline"]["hbm_measured"] = {"bytes_per_step": bps, "achieved": mg, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": mg / HBM_PEAK_GBS,
-                                               "source": pmc.get("_source")}
-        fps = pmc.get("k_rk4_fp64_flop_per_ray_step")
-        if fps and rk4_ms > 0:
-            tf = fps * local_steps_per_pass * args.steps / (rk4_ms * 1e-3) / 1e12
-            # the honest "how busy is the binding unit" figure beside the contract's HBM roofline
-            out["roofline"]["fp64"] = {"flop_per_step": fps, "achieved": tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                       "frac": tf / FP64_PEAK_TFLOPS, "source": pmc.get("_source")}
-        # issue-side roofline of the dominant kernel: the pass lasts as long as the serial integration of its longest ray, one wave alone on its
-        # SIMD issues at most one instruction per 4 cycles - floor = static instructions per step x 4 cycles / 2.4 GHz against the measured time per step
-        isa = newest_isa_mix()
-        longest = int(run.longest_ray_steps) if getattr(run, "longest_ray_steps", 0) else 0
-        if isa and longest and rk4_ms > 0:
-            n_ins = isa["in_line_blocks_skipped"]["instructions"] + isa.get("step_size_block_instructions", 0)
-            meas_us = rk4_ms / args.steps / longest * 1e3
-            out["roofline"]["issue"] = {"instructions_per_step": n_ins, "cycles_per_instruction_floor": 4, "clock_ghz": 2.4, "floor_us_per_step": n_ins * 4 / 2.4e3,
-                                        "measured_us_per_step": meas_us, "frac": (n_ins * 4 / 2.4e3) / meas_us, "longest_ray_steps": longest,
-                                        "cycles_per_instruction_measured": meas_us * 2.4e3 / n_ins, "source": isa.get("_source"),
-                                        "what": "k_rk4<EqGlobalPair>: static instructions of the step loop's common path (tools/isa_mix.py --trace) x 4 cycles against "
-                                                "RK4 time per pass / steps of the longest ray"}
+        if args.full:
+            rk4_ms, post_ms, rk4_launches = ev["ms_rk4"], ev["ms_post"], ev["epochs"]
+            # dominant kernel = k_rk4: algorithmic bytes per launch / average launch duration (HIP events on the kernel's own stream,
+            # recorded inside libgeoac_hip around every k_rk4 epoch of the timed passes).  One epoch of this fan is TWO concurrent k_rk4
+            # launches of the same duration by construction (the shallow tenth of the rays on k_rk4<EqGlobalPair>, the rest on
+            # k_rk4<EqGlobal<true>> with 0.75 x the rows); "launch" below = that pair, bytes and steps are those of both.
+            ach_gbs = (B_ALG_PER_STEP * local_steps_per_pass * args.steps) / (rk4_ms * 1e-3) / 1e9 if rk4_ms > 0 else 0.0
+            pmc = newest_pmc()
+            bps = pmc.get("k_rk4_hbm_bytes_per_ray_step")
+            steps_per_launch = local_steps_per_pass * args.steps / max(rk4_launches, 1)
+            out.update({
+                "parity_gate": gate,
+                "launch_only": {"value": local_steps_per_pass * args.steps * (n_gpus if args.scaling == "weak" else 1) / (ev["ms_total"] * 1e-3) if ev["ms_total"] > 0 and world == 1 else None,
+                                "ms_per_step": ev["ms_total"] / args.steps, "what": "HIP events around the kernels of a pass on this rank, no copies"},
+                "roofline": {"bound": "fp64_valu_latency",
+                             "bound_note": "a register-resident FP64 ODE recurrence: the pass lasts as long as the serial integration of its longest ray; "
+                                           "`achieved`/`frac` are the SURVEY 8(d) contract figure (144 B per step against HBM peak), `hbm_measured` the counter bytes, `fp64` the issue-side figure",
+                             "achieved": ach_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": ach_gbs / HBM_PEAK_GBS,
+                             "traffic": (bps * steps_per_launch) if bps else None, "traffic_unit": "bytes per launch",
+                             "traffic_source": pmc.get("_source"), "traffic_stale": pmc.get("_stale"), "build_id": pmc.get("_build_id_now"),
+                             "traffic_note": "PMC counters (FETCH_SIZE x 2 + WRITE_SIZE, separate rocprofv3 passes of this command) cannot be collected inside the run: "
+                                             "they come from the named profile; traffic_stale = the profiled library is not the one loaded now",
+                             "achieved_bytes_per_launch": B_ALG_PER_STEP * steps_per_launch,
+                             "kernel": "k_rk4<EqGlobalPair,true,false> || k_rk4<EqGlobal<true>,true,false> (one epoch)", "launches": rk4_launches,
+                             "avg_launch_ms": rk4_ms / max(rk4_launches, 1),
+                             "alg_bytes_per_step": B_ALG_PER_STEP,
+                             "rk4_ms_per_pass": rk4_ms / args.steps, "postpass_ms_per_pass": post_ms / args.steps},
+            })
+            if bps and rk4_ms > 0:
+                mg = bps * local_steps_per_pass * args.steps / (rk4_ms * 1e-3) / 1e9
+                out["roofline"]["hbm_measured"] = {"bytes_per_step": bps, "achieved": mg, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": mg / HBM_PEAK_GBS,
+                                                   "source": pmc.get("_source")}
+            fps = pmc.get("k_rk4_fp64_flop_per_ray_step")
+            if fps and rk4_ms > 0:
+                tf = fps * local_steps_per_pass * args.steps / (rk4_ms * 1e-3) / 1e12
+                # the honest "how busy is the binding unit" figure beside the contract's HBM roofline
+                out["roofline"]["fp64"] = {"flop_per_step": fps, "achieved": tf, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                           "frac": tf / FP64_PEAK_TFLOPS, "source": pmc.get("_source")}
+            # issue-side roofline of the dominant kernel: the pass lasts as long as the serial integration of its longest ray, one wave alone on its
+            # SIMD issues at most one instruction per 4 cycles - floor = static instructions per step x 4 cycles / 2.4 GHz against the measured time per step
+            isa = newest_isa_mix()
+            longest = int(run.longest_ray_steps) if getattr(run, "longest_ray_steps", 0) else 0
+            if isa and longest and rk4_ms > 0:
+                n_ins = isa["in_line_blocks_skipped"]["instructions"] + isa.get("step_size_block_instructions", 0)
+                meas_us = rk4_ms / args.steps / longest * 1e3
+                out["roofline"]["issue"] = {"instructions_per_step": n_ins, "cycles_per_instruction_floor": 4, "clock_ghz": 2.4, "floor_us_per_step": n_ins * 4 / 2.4e3,
+                                            "measured_us_per_step": meas_us, "frac": (n_ins * 4 / 2.4e3) / meas_us, "longest_ray_steps": longest,
+                                            "cycles_per_instruction_measured": meas_us * 2.4e3 / n_ins, "source": isa.get("_source"),
+                                            "what": "k_rk4<EqGlobalPair>: static instructions of the step loop's common path (tools/isa_mix.py --trace) x 4 cycles against "
+                                                    "RK4 time per pass / steps of the longest ray"}
         if world > 1:
             out["scaling_note"] = ("weak: per-GPU work fixed (360 azimuths x 90 inclinations per GPU, fan of N x 360 azimuths); the fixed 360x90 fan does NOT strong-scale - "
                                    "one GPU already integrates it in the time of its longest ray (54 130 steps x the step latency), expected ~1.0-1.1x at 8 GPUs; its measured figure "

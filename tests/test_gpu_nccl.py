@@ -23,7 +23,7 @@ def _free_port():
 def test_bench_flow_over_rccl_with_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--force-collective", "--backend", "nccl"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--force-collective", "--backend", "nccl"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]
@@ -39,7 +39,7 @@ def test_bench_gpus_2_starts_its_two_ranks_itself():
     GPU), relay their JSON line and merge the host-side cpu_baseline.  gloo: both ranks share the one GPU of this box (the RCCL transport is
     covered above); weak scaling, so the fan has 720 azimuths and the parity gate checks every second one against the reference's fan."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--no-extras"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "1", "--full", "--no-extras"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]

@@ -19,7 +19,7 @@ def gold():
 
 @pytest.fixture(scope="module")
 def grid(tmp_path_factory):
-    return RD.write_grid(str(tmp_path_factory.mktemp("gd")))
+    return RD.write_grid(str(tmp_path_factory.mktemp("gd")), short_paths=False)
 
 
 def _ctx(grid, **params):

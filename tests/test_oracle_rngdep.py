@@ -18,7 +18,7 @@ def gold():
 def oracle(tmp_path_factory):
     d = tmp_path_factory.mktemp("gd")
     O = H.Oracle(EQ, met=None)
-    O.load_grid(*RD.write_grid(str(d)))
+    O.load_grid(*RD.write_grid(str(d), short_paths=False))          # the oracle takes paths of any length
     return O
 
 
