@@ -191,6 +191,7 @@ class FanContext:
             self._chk(self.lib.geoac_set_stream(self._h, ctypes.c_void_p(stream)))
         self.params = default_params(eqset)
         self.n_rays = 0
+        self.n_members = 1
 
     def _chk(self, rc):
         if rc:
@@ -216,6 +217,7 @@ class FanContext:
         self._chk(self.lib.geoac_clone(self._h, ctypes.byref(c._h)))
         c.params = Params.from_buffer_copy(bytes(self.params))
         c.n_rays = 0
+        c.n_members = 1
         if hasattr(self, "_grid_dims"):
             c._grid_dims = self._grid_dims
         return c
@@ -226,6 +228,34 @@ class FanContext:
             slopes4 = np.concatenate([natural_spline_slopes(x, f) for f in (T, u, v, rho)])
         slopes4 = _arr(slopes4)
         self._chk(self.lib.geoac_upload_atmo_1d(self._h, len(x), _p(x), _p(T), _p(u), _p(v), _p(rho), _p(slopes4)))
+        self.n_members = 1
+
+    def upload_atmo_1d_ensemble(self, x, T, u, v, rho, slopes4=None):
+        """K profiles on the shared nodes x (geoac_upload_atmo_1d_ensemble): T, u, v, rho [K][n]; slopes4 [K][4 n] (default: natural-spline
+        slopes per member and field, as upload_atmo_1d).  fetch() / run() then return records of shape (K, n_rays, legs, 32)."""
+        x = _arr(x)
+        T, u, v, rho = (np.atleast_2d(_arr(a)) for a in (T, u, v, rho))
+        K, n = T.shape
+        if any(a.shape != (K, n) for a in (u, v, rho)) or x.shape != (n,):
+            raise GeoAcError(f"upload_atmo_1d_ensemble: T, u, v, rho must be [K][n] arrays with n = len(x) (got x {x.shape}, T {T.shape}, u {u.shape}, v {v.shape}, rho {rho.shape})")
+        if slopes4 is None:
+            slopes4 = np.stack([np.concatenate([natural_spline_slopes(x, f[m]) for f in (T, u, v, rho)]) for m in range(K)])
+        slopes4 = _arr(slopes4)
+        if slopes4.size != K * 4 * n:
+            raise GeoAcError(f"upload_atmo_1d_ensemble: slopes4 must hold [K][4 n] = {K * 4 * n} values (got {slopes4.size})")
+        self._chk(self.lib.geoac_upload_atmo_1d_ensemble(self._h, K, n, _p(x), _p(T), _p(u), _p(v), _p(rho), _p(slopes4)))
+        self.n_members = K
+
+    def load_met_ensemble(self, paths, fmt="zTuvdp"):
+        """one .met profile per member; the files must share their altitude column"""
+        prof = [met_load(pth, self.eqset, fmt) for pth in paths]
+        if not prof:
+            raise GeoAcError("load_met_ensemble: no profiles")
+        for pth, a in zip(paths[1:], prof[1:]):
+            if a["x"].shape != prof[0]["x"].shape or not np.array_equal(a["x"], prof[0]["x"]):
+                raise GeoAcError(f"load_met_ensemble: {pth} has other altitude nodes than {paths[0]} (an ensemble's members share their nodes)")
+        self.upload_atmo_1d_ensemble(prof[0]["x"], *[np.stack([a[k] for a in prof]) for k in ("T", "u", "v", "rho")])
+        return prof
 
     def upload_atmo_3d(self, x, y, z, T, u, v, rho):
         """grid of profiles: fields [nx][ny][nz] (winds already tapered, km/s)"""
@@ -283,14 +313,15 @@ class FanContext:
 
     def fetch(self, out=None):
         """records of the last launch; `out`: caller-owned C-contiguous float64 array [n_rays][legs][32] (e.g. the numpy view of a pinned
-        torch tensor) to copy into instead of a fresh array"""
+        torch tensor) to copy into instead of a fresh array.  Ensembles (n_members > 1): [K][n_rays][legs][32]"""
         legs = self.params.bounces + 1
+        shape = (self.n_rays, legs, REC_STRIDE) if self.n_members == 1 else (self.n_members, self.n_rays, legs, REC_STRIDE)
         if out is None:
-            rec = np.empty((self.n_rays, legs, REC_STRIDE))
+            rec = np.empty(shape)
         else:
             rec = out
-            if not (isinstance(rec, np.ndarray) and rec.dtype == np.float64 and rec.flags.c_contiguous and rec.shape == (self.n_rays, legs, REC_STRIDE)):
-                raise GeoAcError(f"fetch(out=): need a C-contiguous float64 array of shape {(self.n_rays, legs, REC_STRIDE)}")
+            if not (isinstance(rec, np.ndarray) and rec.dtype == np.float64 and rec.flags.c_contiguous and rec.shape == shape):
+                raise GeoAcError(f"fetch(out=): need a C-contiguous float64 array of shape {shape}")
         steps = ctypes.c_uint64(0)
         self._chk(self.lib.geoac_fan_fetch(self._h, _p(rec), ctypes.byref(steps)))
         return rec, int(steps.value)

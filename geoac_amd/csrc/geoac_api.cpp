@@ -36,7 +36,7 @@ extern "C" hipError_t geoac_gridbuild_launch(int glob, int nx, int ny, int nz, c
                                              const double* d_fields, double* d_work, double* d_tab, hipStream_t s);
 extern "C" hipError_t geoac_launch_accum(const GeoacDevParams* P, hipStream_t s);
 extern "C" hipError_t geoac_launch_arrival(const GeoacDevParams* P, hipStream_t s);
-extern "C" hipError_t geoac_launch_compact(const GeoacDevParams* P, const int* cur, const int* n_cur, int n_first, int* next, int* n_next, hipStream_t s);
+extern "C" hipError_t geoac_launch_compact(const GeoacDevParams* P, const int* cur, const int* n_cur, int n_first, int* next, int* n_next, int align, hipStream_t s);
 extern "C" hipError_t geoac_launch_probe_atmo1d(const GeoacDevParams* P, int n, const double* x, double* out9, double* rho, hipStream_t s);
 extern "C" hipError_t geoac_launch_probe_absorption(const GeoacDevParams* P, int n, const double* x, const double* f, double* out, hipStream_t s);
 extern "C" hipError_t geoac_launch_probe_atab(const GeoacDevParams* P, int n, const double* x, double* out, hipStream_t s);
@@ -188,6 +188,7 @@ struct geoac_ctx {
     // absorption table of the stratified sets (k_atab_build): rebuilt when the atmosphere or one of the parameters it depends on changes
     bool abs_table = true;                        // GEOAC_ABS_TABLE=0: exact Sutherland-Bass evaluation at every segment midpoint (A/B runs, equivalence test)
     DevBuf atab;
+    std::vector<double> atab_mkey;                // the members' reference states the table was built for
     DevBuf ppfix;                                 // fix-up list of the table post-pass (k_postpass_tab -> k_ppfix)
     double atab_tol = 1e-10;                      // ABS_TABLE_TOL: relative error at its check points above which a table entry is flagged
     int ppfix_cap = 1 << 20;                      // PPFIX_CAP: segments per epoch the table may leave to k_ppfix (8 MB); more: the fan is repeated with the exact post-pass
@@ -196,6 +197,14 @@ struct geoac_ctx {
     int atab_entries = 0, atab_flagged = 0;       // of the current table
     double atab_worst = 0;                        // largest relative error the build saw at its check points, unflagged entries
     unsigned long long pp_fixup_segments = 0;     // last launch: path segments the table did not serve (evaluated exactly)
+    // ensembles (geoac_upload_atmo_1d_ensemble): K profiles on the nodes in x; the tables above hold K member tables back to back, the host copies x, T, u, v, rho, sl
+    // member 0 (geoac_medium_1d, the probes); ens_T, ens_rho, ens_sl every member's (the reference state of the absorption model, per member)
+    int n_members = 1;
+    int mem_slots = 0;                            // ray slots per member of the current angle layout (K > 1)
+    std::vector<double> ens_T, ens_rho, ens_sl;
+    std::vector<double> mconsts;                  // [K][GEOAC_MEMC] of the last launch
+    DevBuf d_mconsts;
+    std::vector<double> ang_th, ang_ph;           // the caller's launch angles (the slot layout is rebuilt when K changes)
     std::string err;
 };
 
@@ -386,7 +395,7 @@ int geoac_destroy(geoac_ctx* ctx){
     ctx->atmo_gen->store(~0ull);                                  // (clones of this context must not launch on its freed tables)
     hipSetDevice(ctx->device);
     if(ctx->stream) hipStreamSynchronize(ctx->stream);
-    DevBuf* bufs[] = { &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
+    DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->nrows[0], &ctx->nrows[1], &ctx->nrows[2], &ctx->legend[0], &ctx->legend[1], &ctx->legend[2],
                        &ctx->nlegend[0], &ctx->nlegend[1], &ctx->nlegend[2],
@@ -419,6 +428,7 @@ int geoac_destroy(geoac_ctx* ctx){
 int geoac_clone(geoac_ctx* src, geoac_ctx** out){
     if(!src || !out) return GEOAC_E_INVALID;
     if(!src->have_atmo) return fail(src, GEOAC_E_INVALID, "clone: no atmosphere uploaded");
+    if(src->n_members > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
     geoac_ctx* c = nullptr;
     int rc = geoac_create(&c, src->eqset, src->device);
     if(rc) return rc;
@@ -448,26 +458,29 @@ int geoac_set_stream(geoac_ctx* ctx, void* hip_stream){
     return GEOAC_OK;
 }
 
-int geoac_upload_atmo_1d(geoac_ctx* ctx, int n, const double* x, const double* T, const double* u,
-                         const double* v, const double* rho, const double* slopes4){
-    if(!ctx || n < 3 || !x || !T || !u || !v || !rho || !slopes4) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d: bad arguments");
-    if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
-        return fail(ctx, GEOAC_E_UNSUPPORTED, "1-D atmosphere on a range-dependent equation set");
-    for(int i = 1; i < n; i++) if(!(x[i] > x[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d: abscissa not strictly increasing");
+static int layout_angles(geoac_ctx* ctx);
+
+// K profiles on the nodes x (K = 1: geoac_upload_atmo_1d); T, u, v, rho [K][n], slopes4 [K][4 n]
+static int upload_members(geoac_ctx* ctx, int K, int n, const double* x, const double* T, const double* u,
+                          const double* v, const double* rho, const double* slopes4){
     HIPCHK(hipSetDevice(ctx->device));
+    const size_t nn = (size_t)n;
     ctx->n_nodes = n;
     ctx->x.assign(x, x + n); ctx->T.assign(T, T + n); ctx->u.assign(u, u + n); ctx->v.assign(v, v + n); ctx->rho.assign(rho, rho + n);
-    ctx->sl.assign(slopes4, slopes4 + 4 * (size_t)n);
-    const double* sT = slopes4; const double* su = slopes4 + n; const double* sv = slopes4 + 2 * (size_t)n; const double* sr = slopes4 + 3 * (size_t)n;
+    ctx->sl.assign(slopes4, slopes4 + 4 * nn);
     int nseg = n - 1;
-    std::vector<double> seg((size_t)nseg * GEOAC_SEGW), rt((size_t)nseg * 4);
+    std::vector<double> seg((size_t)K * nseg * GEOAC_SEGW), rt((size_t)K * nseg * 4);
+    for(int m = 0; m < K; m++){
+    const double* Tm = T + m * nn; const double* um = u + m * nn; const double* vm = v + m * nn; const double* rm = rho + m * nn;
+    const double* sT = slopes4 + 4 * nn * m; const double* su = sT + n; const double* sv = sT + 2 * nn; const double* sr = sT + 3 * nn;
     for(int k = 0; k < nseg; k++){
-        double* s = &seg[(size_t)k * GEOAC_SEGW];
+        double* s = &seg[((size_t)m * nseg + k) * GEOAC_SEGW];
         s[0] = x[k]; s[1] = x[k + 1];
-        seg_coeffs(x[k], x[k + 1], T[k], T[k + 1], sT[k], sT[k + 1], s + 2, true);
-        seg_coeffs(x[k], x[k + 1], u[k], u[k + 1], su[k], su[k + 1], s + 6, true);
-        seg_coeffs(x[k], x[k + 1], v[k], v[k + 1], sv[k], sv[k + 1], s + 10, true);
-        seg_coeffs(x[k], x[k + 1], rho[k], rho[k + 1], sr[k], sr[k + 1], &rt[(size_t)k * 4], false);
+        seg_coeffs(x[k], x[k + 1], Tm[k], Tm[k + 1], sT[k], sT[k + 1], s + 2, true);
+        seg_coeffs(x[k], x[k + 1], um[k], um[k + 1], su[k], su[k + 1], s + 6, true);
+        seg_coeffs(x[k], x[k + 1], vm[k], vm[k + 1], sv[k], sv[k + 1], s + 10, true);
+        seg_coeffs(x[k], x[k + 1], rm[k], rm[k + 1], sr[k], sr[k + 1], &rt[((size_t)m * nseg + k) * 4], false);
+    }
     }
     HIPCHK(ctx->seg.ensure(seg.size() * sizeof(double)));
     HIPCHK(ctx->rhot.ensure(rt.size() * sizeof(double)));
@@ -479,6 +492,45 @@ int geoac_upload_atmo_1d(geoac_ctx* ctx, int n, const double* x, const double* T
     ctx->have_atmo = true;
     ctx->atmo_version++; ctx->atmo_gen->fetch_add(1);
     ctx->ran = false;                             // (the probes launch with the tables of the last fan: not after a new upload)
+    const int K_was = ctx->n_members;
+    ctx->n_members = K;
+    if(K > 1){ ctx->ens_T.assign(T, T + K * nn); ctx->ens_rho.assign(rho, rho + K * nn); ctx->ens_sl.assign(slopes4, slopes4 + 4 * nn * K); }
+    else { ctx->ens_T.clear(); ctx->ens_rho.clear(); ctx->ens_sl.clear(); }
+    if(K != K_was && ctx->have_angles) return layout_angles(ctx);       // (the slot layout depends on K)
+    return GEOAC_OK;
+}
+
+int geoac_upload_atmo_1d(geoac_ctx* ctx, int n, const double* x, const double* T, const double* u,
+                         const double* v, const double* rho, const double* slopes4){
+    if(!ctx || n < 3 || !x || !T || !u || !v || !rho || !slopes4) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d: bad arguments");
+    if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "1-D atmosphere on a range-dependent equation set");
+    for(int i = 1; i < n; i++) if(!(x[i] > x[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d: abscissa not strictly increasing");
+    return upload_members(ctx, 1, n, x, T, u, v, rho, slopes4);
+}
+
+int geoac_upload_atmo_1d_ensemble(geoac_ctx* ctx, int n_members, int n, const double* x, const double* T, const double* u,
+                                  const double* v, const double* rho, const double* slopes4){
+    if(!ctx) return GEOAC_E_INVALID;
+    if(n_members < 1 || n_members > GEOAC_MAX_MEMBERS)
+        return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d_ensemble: n_members must be in 1 .. " + std::to_string(GEOAC_MAX_MEMBERS));
+    if(n < 3) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d_ensemble: at least 3 nodes");
+    if(!x || !T || !u || !v || !rho || !slopes4) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d_ensemble: NULL array");
+    if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "upload_atmo_1d_ensemble: ensembles are available for the stratified equation sets only");
+    for(int i = 1; i < n; i++) if(!(x[i] > x[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_1d_ensemble: abscissa not strictly increasing");
+    return upload_members(ctx, n_members, n, x, T, u, v, rho, slopes4);
+}
+
+// the callers inside the library that take one profile per context (eigenray searches, the pool): GEOAC_E_UNSUPPORTED with a message for an ensemble
+int geoac_refuse_ensemble(geoac_ctx* ctx, const char* what){
+    if(!ctx || ctx->n_members <= 1) return GEOAC_OK;
+    return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
+}
+
+int geoac_get_members(geoac_ctx* ctx, int* n_members){
+    if(!ctx || !n_members) return fail(ctx, GEOAC_E_INVALID, "get_members: bad arguments");
+    *n_members = ctx->n_members;
     return GEOAC_OK;
 }
 
@@ -530,6 +582,7 @@ int geoac_upload_atmo_3d(geoac_ctx* ctx, int nx, int ny, int nz, const double* x
     } else ctx->d_gtab8.release();
     ctx->gnx = nx; ctx->gny = ny; ctx->n_nodes = nz;
     ctx->gx.assign(x, x + nx); ctx->gy.assign(y, y + ny); ctx->x.assign(z, z + nz);
+    ctx->n_members = 1;
     // GeoAc_SetPropRegion (G2S_MultiDimSpline3D.cpp:25-33)
     if(!(ctx->prm.vert_limit == ctx->prm.vert_limit)) ctx->prm.vert_limit = z[nz - 1];
     const double ext[4] = { x[0], x[nx - 1], y[0], y[ny - 1] };
@@ -590,6 +643,14 @@ int geoac_set_params(geoac_ctx* ctx, const geoac_params* p){
 
 int geoac_fan_set_angles(geoac_ctx* ctx, int n_rays, const double* theta_deg, const double* phi_deg){
     if(!ctx || n_rays <= 0 || !theta_deg || !phi_deg) return fail(ctx, GEOAC_E_INVALID, "fan_set_angles: bad arguments");
+    ctx->ang_th.assign(theta_deg, theta_deg + n_rays); ctx->ang_ph.assign(phi_deg, phi_deg + n_rays);
+    return layout_angles(ctx);
+}
+
+// slot layout of the fan in ang_th / ang_ph: the sort of the rays, and for an ensemble the member-major copies of it
+static int layout_angles(geoac_ctx* ctx){
+    const int n_rays = (int)ctx->ang_th.size();
+    const double* theta_deg = ctx->ang_th.data(); const double* phi_deg = ctx->ang_ph.data();
     HIPCHK(hipSetDevice(ctx->device));
     ctx->n_rays = n_rays;
     ctx->n_pad = (n_rays + 63) / 64 * 64;
@@ -652,6 +713,23 @@ int geoac_fan_set_angles(geoac_ctx* ctx, int n_rays, const double* theta_deg, co
         HIPCHK(hipMemcpyAsync(ctx->perm.p, order.data(), sizeof(int) * (size_t)ctx->n_pad, hipMemcpyHostToDevice, ctx->stream));
         ctx->have_perm = true;
     }
+    std::vector<int> eo; std::vector<double> et, ep;
+    if(ctx->n_members > 1){
+        // ensembles: member m owns the slots [m S, (m+1) S), each a copy of the single fan's layout; S: a multiple of the widest RK4 workgroup
+        // with at least one slot without a ray (the padding columns of the segmented compaction name it)
+        const int K = ctx->n_members, S = (n_rays + 1 + 255) / 256 * 256;
+        eo.assign((size_t)K * S, -1); et.assign((size_t)K * S, 0.0); ep.assign((size_t)K * S, 0.0);
+        for(int m = 0; m < K; m++)
+            for(int j = 0; j < n_rays; j++){
+                const int r = ctx->have_perm ? order[(size_t)j] : j;
+                eo[(size_t)m * S + j] = m * n_rays + r; et[(size_t)m * S + j] = theta_deg[r]; ep[(size_t)m * S + j] = phi_deg[r];
+            }
+        ctx->n_pad = K * S; ctx->mem_slots = S;
+        HIPCHK(ctx->perm.ensure(sizeof(int) * eo.size()));
+        HIPCHK(hipMemcpyAsync(ctx->perm.p, eo.data(), sizeof(int) * eo.size(), hipMemcpyHostToDevice, ctx->stream));
+        ctx->have_perm = true;
+        th_up = et.data(); ph_up = ep.data(); n_up = et.size();
+    }
     HIPCHK(ctx->theta.ensure(sizeof(double) * (size_t)ctx->n_pad));
     HIPCHK(ctx->phi.ensure(sizeof(double) * (size_t)ctx->n_pad));
     HIPCHK(hipMemcpyAsync(ctx->theta.p, th_up, sizeof(double) * n_up, hipMemcpyHostToDevice, ctx->stream));
@@ -670,9 +748,14 @@ static int fan_launch_once(geoac_ctx* ctx){
     if(is_grid != ctx->have_grid) return fail(ctx, GEOAC_E_INVALID, "fan_launch: atmosphere kind does not match the equation set");
     HIPCHK(hipSetDevice(ctx->device));
     const geoac_params& p = ctx->prm;
+    const int K = ctx->n_members;
+    const bool ens = K > 1;
+    if(ens && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available for an ensemble; run the member on a context of its own");
     GeoacDevParams P{};
     P.eqset = ctx->eqset; P.calc_amp = p.calc_amp ? 1 : 0; P.mode = p.mode; P.bounces = p.bounces;
-    P.n_rays = ctx->n_rays; P.n_pad = ctx->n_pad;
+    P.n_rays = ctx->n_rays * K; P.n_pad = ctx->n_pad;
+    P.n_members = K; P.mem_slots = ens ? ctx->mem_slots : 0; P.mem_consts = nullptr;
     const bool is_global = (ctx->eqset == GEOAC_EQ_GLOBAL);                                  // stratified spherical set (pair kernel, range test)
     const bool is_sph = is_global || ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP;                   // geocentric radius as the height coordinate
     if(is_global){ P.E = p.calc_amp ? 18 : 6; P.pathw = 6; }
@@ -704,13 +787,31 @@ static int fan_launch_once(geoac_ctx* ctx){
         P.sb_const[0] = pow(10.0, -0.67887); P.sb_const[1] = pow(10.0, -0.10744); P.sb_const[2] = pow(10, -3.3979);
         P.sb_const[3] = 5.0 / sqrt(21.0); P.sb_const[4] = sqrt(3.0 / 7.0);
         if(is_grid){ P.T_o = P.P_o = 0.0; P.c000 = 0.0; } else {
-        double Tg = host_spline_f(ctx->x, ctx->T, ctx->sl.data(), p.z_grnd);
-        double rg = host_spline_f(ctx->x, ctx->rho, ctx->sl.data() + 3 * (size_t)ctx->n_nodes, p.z_grnd);
+        // (ensembles: per member, the same evaluation on each member's profile; the block carries member 0's, the kernels' member view the others')
+        const size_t nn = (size_t)ctx->n_nodes;
+        ctx->mconsts.assign((size_t)K * GEOAC_MEMC, 0.0);
+        std::vector<double> Tm, rm;
+        for(int m = 0; m < K; m++){
+        if(ens){ Tm.assign(ctx->ens_T.begin() + m * nn, ctx->ens_T.begin() + (m + 1) * nn); rm.assign(ctx->ens_rho.begin() + m * nn, ctx->ens_rho.begin() + (m + 1) * nn); }
+        const std::vector<double>& Tv = ens ? Tm : ctx->T;
+        const std::vector<double>& rv = ens ? rm : ctx->rho;
+        const double* slm = ens ? ctx->ens_sl.data() + 4 * nn * m : ctx->sl.data();
+        double Tg = host_spline_f(ctx->x, Tv, slm, p.z_grnd);
+        double rg = host_spline_f(ctx->x, rv, slm + 3 * nn, p.z_grnd);
         double cg = sqrt(kGamR * Tg) * 1000.0;
         P.T_o = cg * cg / (kRgas * kGam);
         P.cbrt_To = cbrt(P.T_o);
         P.P_o = rg * (cg * cg) / kGam * 1000.0;
-        P.c000 = sqrt(kGamR * host_spline_f(ctx->x, ctx->T, ctx->sl.data(), 0.0));       // c(0,0,0), 3DStratified.cpp:367
+        P.c000 = sqrt(kGamR * host_spline_f(ctx->x, Tv, slm, 0.0));       // c(0,0,0), 3DStratified.cpp:367
+        double* c = &ctx->mconsts[(size_t)m * GEOAC_MEMC];
+        c[0] = P.T_o; c[1] = P.P_o; c[2] = P.cbrt_To; c[3] = P.c000;
+        }
+        P.T_o = ctx->mconsts[0]; P.P_o = ctx->mconsts[1]; P.cbrt_To = ctx->mconsts[2]; P.c000 = ctx->mconsts[3];
+        if(ens){
+            HIPCHK(ctx->d_mconsts.ensure(sizeof(double) * ctx->mconsts.size()));
+            HIPCHK(hipMemcpy(ctx->d_mconsts.p, ctx->mconsts.data(), sizeof(double) * ctx->mconsts.size(), hipMemcpyHostToDevice));
+            P.mem_consts = (const double*)ctx->d_mconsts.p;
+        }
         }
         P.src_trig[0] = sin(p.src[1] * kPi / 180.0); P.src_trig[1] = cos(p.src[1] * kPi / 180.0);
     }
@@ -759,7 +860,7 @@ static int fan_launch_once(geoac_ctx* ctx){
         HIPCHK(ctx->smp_out.ensure(sizeof(double) * GEOAC_SMP_STRIDE * (size_t)P.smp_cap));
         P.smp_out = (double*)ctx->smp_out.p;
     }
-    HIPCHK(ctx->rec.ensure(sizeof(double) * (size_t)ctx->n_rays * ctx->legs * GEOAC_REC_STRIDE));
+    HIPCHK(ctx->rec.ensure(sizeof(double) * (size_t)P.n_rays * ctx->legs * GEOAC_REC_STRIDE));
     HIPCHK(ctx->counters.ensure(32 * sizeof(unsigned long long)));
     P.seg = (const double*)ctx->seg.p; P.rho = (const double*)ctx->rhot.p;
     P.theta_deg = (const double*)ctx->theta.p; P.phi_deg = (const double*)ctx->phi.p;
@@ -773,25 +874,34 @@ static int fan_launch_once(geoac_ctx* ctx){
         const double D = std::max(std::min(0.05, p.ds_max), p.ds_min), tol = ctx->atab_tol;
         const double key[7] = { P.freq, P.tweak_abs, P.T_o, P.P_o, P.r_earth, D, tol };
         P.atab_D = D; P.atab_lo = P.x_min - D;
-        if(ctx->atab_version != ctx->atmo_version || memcmp(key, ctx->atab_key, sizeof(key)) != 0){
-            const size_t n_ent = (size_t)P.nseg + 2;
-            HIPCHK(ctx->atab.ensure(sizeof(double) * (GEOAC_ATABW * n_ent + 2 * (size_t)GEOAC_LAT_N)));      // (+ the latitude table behind it)
-            HIPCHK(geoac_launch_atab_build(&P, (double*)ctx->atab.p, tol, ctx->stream));
-            std::vector<double> h(GEOAC_ATABW * n_ent);
+        const size_t n_ent = (size_t)P.nseg + 2;
+        if(ctx->atab_version != ctx->atmo_version || memcmp(key, ctx->atab_key, sizeof(key)) != 0 || ctx->atab_mkey != ctx->mconsts){
+            HIPCHK(ctx->atab.ensure(sizeof(double) * (GEOAC_ATABW * n_ent * K + 2 * (size_t)GEOAC_LAT_N)));      // (+ the latitude table behind the last one)
+            // ensembles: one launch per member on the host-side member view, in member order - each launch also writes the latitude table behind
+            // its own table, where the next member's table then goes: the last launch leaves it behind the last table
+            for(int m = 0; m < K; m++){
+                GeoacDevParams Pm = P;
+                Pm.seg = (const double*)ctx->seg.p + (size_t)m * P.nseg * GEOAC_SEGW; Pm.rho = (const double*)ctx->rhot.p + (size_t)m * P.nseg * 4;
+                const double* c = &ctx->mconsts[(size_t)m * GEOAC_MEMC];
+                Pm.T_o = c[0]; Pm.P_o = c[1]; Pm.cbrt_To = c[2]; Pm.c000 = c[3];
+                HIPCHK(geoac_launch_atab_build(&Pm, (double*)ctx->atab.p + GEOAC_ATABW * n_ent * m, tol, ctx->stream));
+            }
+            std::vector<double> h(GEOAC_ATABW * n_ent * K);
             HIPCHK(hipMemcpyAsync(h.data(), ctx->atab.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            ctx->atab_entries = (int)n_ent; ctx->atab_flagged = 0; ctx->atab_worst = 0.0;
-            for(size_t e = 0; e < n_ent; e++){
+            ctx->atab_entries = (int)(n_ent * K); ctx->atab_flagged = 0; ctx->atab_worst = 0.0;
+            for(size_t e = 0; e < n_ent * K; e++){
                 if(h[e * GEOAC_ATABW] < 0.0) ctx->atab_flagged++;
                 else ctx->atab_worst = std::max(ctx->atab_worst, h[e * GEOAC_ATABW + GEOAC_ATABW - 1]);
             }
             memcpy(ctx->atab_key, key, sizeof(key));
+            ctx->atab_mkey = ctx->mconsts;
             ctx->atab_version = ctx->atmo_version;
         }
         // a profile most of whose segments the interpolant cannot serve (very long segments) keeps the exact post-pass
         if(4 * ctx->atab_flagged <= ctx->atab_entries){
             P.atab = (const double*)ctx->atab.p; P.atab_on = 1;
-            P.lat_trig = P.atab + (size_t)GEOAC_ATABW * ((size_t)P.nseg + 2);
+            P.lat_trig = P.atab + (size_t)GEOAC_ATABW * n_ent * K;
             P.ppfix_cap = ctx->ppfix_cap;
             HIPCHK(ctx->ppfix.ensure(sizeof(int) * 2 * (size_t)P.ppfix_cap));
             P.ppfix = (int*)ctx->ppfix.p;
@@ -808,15 +918,17 @@ static int fan_launch_once(geoac_ctx* ctx){
     P.pp_blocks = ctx->pp_blocks;
     P.slot_lo = 0; P.slot_hi = P.n_pad; P.live_slot = 1;
     // two lanes per ray shorten the serial chain (x1.25) at twice the lanes: only worth it while the fan leaves SIMDs idle
-    P.lanes_per_ray = ((is_global || ctx->eqset == GEOAC_EQ_3D) && p.calc_amp && !sampling && !ctx->no_pair && (long long)P.n_pad * 2 / 64 <= 1024) ? 2 : 1;
+    P.lanes_per_ray = ((is_global || ctx->eqset == GEOAC_EQ_3D) && p.calc_amp && !sampling && !ctx->no_pair && !ens && (long long)P.n_pad * 2 / 64 <= 1024) ? 2 : 1;
+    // ensembles run the one-lane kernels with none of the plans tuned for single fans (pair, DUO / TRIO, hybrid, stagger, late pair, CU_SPLIT): records do not
+    // depend on the plan, and K fans together fill the chip the way those plans tried to
     // Global set with amplitudes, arrivals only, a fan of at most one workgroup per CU (128 rays each) and a profile whose packed table
     // leaves room for the message slots: the wave-specialised kernel (geoac_duo.h) - the ray on one wave, its two launch-angle derivative
     // systems on a second one
-    P.duo = (is_global && p.calc_amp && !sampling && ctx->duo && !ctx->no_pair && P.table_in_lds && geoac_duo_lds(P.nseg) <= 160 * 1024 &&
+    P.duo = (is_global && p.calc_amp && !sampling && !ens && ctx->duo && !ctx->no_pair && P.table_in_lds && geoac_duo_lds(P.nseg) <= 160 * 1024 &&
              (long long)P.n_pad <= 256ll * 128) ? ctx->duo : 0;
     if(P.duo) P.lanes_per_ray = 1;
     // ... or the three-wave one (geoac_trio.h) for the slots the plan gives two lanes per ray: 64 rays per workgroup
-    P.trio = (!P.duo && is_global && p.calc_amp && !sampling && ctx->trio && P.lanes_per_ray == 2 && P.table_in_lds && geoac_trio_lds(P.nseg) <= 160 * 1024) ? ctx->trio : 0;
+    P.trio = (!P.duo && !ens && is_global && p.calc_amp && !sampling && ctx->trio && P.lanes_per_ray == 2 && P.table_in_lds && geoac_trio_lds(P.nseg) <= 160 * 1024) ? ctx->trio : 0;
     // grid sets, small fans: four lanes per ray (one cell corner each) while that still leaves one wave per SIMD
     // (16 385 - 32 768 rays used to take two lanes per ray: measured on MI355X, profiles/r03_midfans.txt, the cooperative one-lane kernel is faster
     // there for the Cartesian set - 4.8e8 against 4.1e8 ray-steps/s at 24 000 rays - and within 5 % for the spherical one, and it uses no scratch)
@@ -884,7 +996,7 @@ static int fan_launch_once(geoac_ctx* ctx){
     // (0.10 / 0.75: 121.8 ms; 0.15: 124.7, 0.20: 126.9); the 3-D set's are spread over the inclinations (0.25 / 0.80: 108 ms; 0.10 / 0.75: 125)
     const double plan_pair_frac = ctx->pair_frac >= 0.0 ? ctx->pair_frac : (P.eqset == GEOAC_EQ_3D ? 0.25 : 0.10);
     const double plan_hybrid_rows = ctx->hybrid_rows > 0.0 ? ctx->hybrid_rows : (P.eqset == GEOAC_EQ_3D ? 0.80 : 0.75);
-    const bool hybrid = (P.lanes_per_ray == 2 && !is_grid && ctx->have_perm && plan_pair_frac < 1.0 && !ctx->no_overlap &&
+    const bool hybrid = (P.lanes_per_ray == 2 && !ens && !is_grid && ctx->have_perm && plan_pair_frac < 1.0 && !ctx->no_overlap &&
                          (long long)P.n_pad * 2 / 64 > 512);   // a fan that leaves half the SIMDs idle anyway keeps two lanes for every ray
     if(hybrid){
         n_pair = (int)(((long long)(plan_pair_frac * ctx->n_rays) + 127) / 128 * 128);
@@ -905,15 +1017,15 @@ static int fan_launch_once(geoac_ctx* ctx){
     //      a 72 000-ray fan 253 -> 213 ms, a 200 000-ray one 415 -> 376, GeoAc3D 720 x 180 312-331 -> 297-303.
     const double plan_stagger_frac = ctx->stagger_frac >= 0.0 ? ctx->stagger_frac : 0.12;
     const double plan_stagger_rows = ctx->stagger_rows > 0.0 ? ctx->stagger_rows : 0.6;
-    bool stagger = compact && !is_grid && !sampling && P.table_in_lds && ctx->have_perm && !ctx->no_overlap && plan_stagger_frac > 0.0 && P.lanes_per_ray == 1 && (long long)P.n_pad / 64 > 1024;   // (arrivals-only fans: what the plan was measured on)
+    bool stagger = compact && !ens && !is_grid && !sampling && P.table_in_lds && ctx->have_perm && !ctx->no_overlap && plan_stagger_frac > 0.0 && P.lanes_per_ray == 1 && (long long)P.n_pad / 64 > 1024;   // (arrivals-only fans: what the plan was measured on)
     const bool stagger_plan = stagger;
     // fans that start with one lane per ray because two would not fit the chip (more than 1 024 two-lane waves): once the rays still alive do fit, the remaining epochs - the
     // serial chain of the few longest rays - run on the two-lane kernel (the same state layout; what a hybrid fan does when its two-lane share has finished)
-    const bool late_pair_able = compact && !is_grid && (is_global || ctx->eqset == GEOAC_EQ_3D) && p.calc_amp && !sampling && !ctx->no_pair && P.table_in_lds && P.lanes_per_ray == 1 && !P.duo;
+    const bool late_pair_able = compact && !ens && !is_grid && (is_global || ctx->eqset == GEOAC_EQ_3D) && p.calc_amp && !sampling && !ctx->no_pair && P.table_in_lds && P.lanes_per_ray == 1 && !P.duo;
     bool late_pair = false;
     unsigned long long long_bound = (unsigned long long)(plan_stagger_frac * ctx->n_rays);      // live rays of the leading share (an upper bound: what its last launch counted)
     if(compact){
-        for(int b = 0; b < 3; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * (size_t)P.n_pad));
+        for(int b = 0; b < 3; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * ((size_t)P.n_pad + K)));      // (ensembles: + the members' range starts)
         HIPCHK(ctx->ncols.ensure(4 * sizeof(int)));
     }
     P.n_cols_bound = P.n_pad;
@@ -954,7 +1066,7 @@ static int fan_launch_once(geoac_ctx* ctx){
     // a round leaves over.  With two streams confined to disjoint sets of CUs (hipExtStreamCreateWithCUMask; the mask's bits go round robin over the XCDs, so either set is
     // spread evenly over the eight of them) both run all the time, each at the occupancy that suits it.
     int cu_split = ctx->cu_split >= 0 ? ctx->cu_split : 0;
-    if(ctx->no_overlap || hybrid || !P.table_in_lds || is_grid) cu_split = 0;
+    if(ctx->no_overlap || hybrid || !P.table_in_lds || is_grid || ens) cu_split = 0;
     if(cu_split > 0){
         int n_cu = 0;
         HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device));
@@ -1046,9 +1158,10 @@ static int fan_launch_once(geoac_ctx* ctx){
             // (after epoch e-2: an upper bound), lanes beyond the device-side count leave at once
             const int pb = (int)((e - 1) % (size_t)n_chunks);
             HIPCHK(geoac_launch_compact(&P, e == 1 ? nullptr : (const int*)ctx->colmap[pb].p, (const int*)ctx->ncols.p + pb, P.n_pad,
-                                        (int*)ctx->colmap[b].p, (int*)ctx->ncols.p + b, s));
+                                        (int*)ctx->colmap[b].p, (int*)ctx->ncols.p + b, block, s));
             Pe.colmap = (const int*)ctx->colmap[b].p; Pe.n_cols = (const int*)ctx->ncols.p + b;
-            Pe.n_cols_bound = (int)std::min<unsigned long long>((unsigned long long)P.n_pad, (live_bound + 63ull) / 64ull * 64ull);
+            // (ensembles: each member's columns padded to whole workgroups)
+            Pe.n_cols_bound = (int)std::min<unsigned long long>((unsigned long long)P.n_pad, (live_bound + 63ull) / 64ull * 64ull + (ens ? (unsigned long long)K * block : 0ull));
             if(Pe.n_cols_bound < 64) Pe.n_cols_bound = 64;
             Pe.slot_lo = 0; Pe.slot_hi = Pe.n_cols_bound;
         }
@@ -1225,14 +1338,14 @@ int geoac_fan_sync(geoac_ctx* ctx){
 int geoac_fan_records_dev(geoac_ctx* ctx, void** dev_ptr, size_t* bytes){
     if(!ctx || !ctx->ran) return fail(ctx, GEOAC_E_INVALID, "fan_records_dev: no completed launch");
     if(dev_ptr) *dev_ptr = ctx->rec.p;
-    if(bytes) *bytes = sizeof(double) * (size_t)ctx->n_rays * ctx->legs * GEOAC_REC_STRIDE;
+    if(bytes) *bytes = sizeof(double) * (size_t)ctx->n_rays * ctx->lastP.n_members * ctx->legs * GEOAC_REC_STRIDE;
     return GEOAC_OK;
 }
 
 int geoac_fan_copy_records_dev(geoac_ctx* ctx, void* dst_dev){
     if(!ctx || !ctx->ran || !dst_dev) return fail(ctx, GEOAC_E_INVALID, "fan_copy_records_dev: no completed launch / null destination");
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipMemcpyAsync(dst_dev, ctx->rec.p, sizeof(double) * (size_t)ctx->n_rays * ctx->legs * GEOAC_REC_STRIDE,
+    HIPCHK(hipMemcpyAsync(dst_dev, ctx->rec.p, sizeof(double) * (size_t)ctx->n_rays * ctx->lastP.n_members * ctx->legs * GEOAC_REC_STRIDE,
                           hipMemcpyDeviceToDevice, ctx->stream));
     return GEOAC_OK;
 }
@@ -1241,7 +1354,7 @@ int geoac_fan_fetch(geoac_ctx* ctx, double* rec_host, uint64_t* total_steps){
     if(!ctx || !ctx->ran) return fail(ctx, GEOAC_E_INVALID, "fan_fetch: no completed launch");
     HIPCHK(hipSetDevice(ctx->device));
     if(rec_host){
-        HIPCHK(hipMemcpyAsync(rec_host, ctx->rec.p, sizeof(double) * (size_t)ctx->n_rays * ctx->legs * GEOAC_REC_STRIDE,
+        HIPCHK(hipMemcpyAsync(rec_host, ctx->rec.p, sizeof(double) * (size_t)ctx->n_rays * ctx->lastP.n_members * ctx->legs * GEOAC_REC_STRIDE,
                               hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }

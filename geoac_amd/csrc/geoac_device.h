@@ -12,6 +12,11 @@
 //                                       (Interface.cpp:53-58) re-laid-out for 64-wide coalescing and cut into epochs.
 //   contrib     [S_rows][2][n_pad]      per-segment travel-time and attenuation increments (post-pass kernel)
 //   records     [n_rays][legs][32]      one arrival record per (ray, leg), layout in include/geoac_hip.h
+//
+// Ensembles (geoac_upload_atmo_1d_ensemble: K profiles on shared nodes, one fan through all of them): the seg, rho and absorption tables
+// are K member tables back to back ([K][nseg][SEGW], [K][nseg][4], [K][nseg+2][ATABW], one lat_trig behind the last), the ray slots are
+// member-major (member m owns [m S, (m+1) S), S = mem_slots, a multiple of 256 with at least one ray-less slot), the records [K][n_rays][legs][32].
+// A kernel instantiated for ensembles finds its member once per workgroup or wave and works on the member view (member_view) of the block.
 #ifndef GEOAC_DEVICE_H_
 #define GEOAC_DEVICE_H_
 
@@ -138,6 +143,12 @@ struct GeoacDevParams {
     long long     smp_cap;
     double*       rec;              // [n_rays][bounces+1][32]
     unsigned long long* counters;   // [0] total steps, [1] active rays after this epoch, [2] error flags, [3] samples emitted
+    // ensembles (n_members > 1); 1 / 0 / NULL for a single profile
+    int           n_members;        // K
+    int           mem_slots;        // S: ray slots per member
+    const double* mem_consts;       // [K][GEOAC_MEMC]: T_o, P_o, cbrt_To, c000 of each member (host-evaluated as for a single profile)
 };
+
+#define GEOAC_MEMC      4       // doubles per member in mem_consts
 
 #endif

@@ -973,6 +973,10 @@ static int run_all(geoac_ctx* ctx, const geoac_eig_params* ep, int n_rcvr, const
     return 0;
 }
 
+// (geoac_api.cpp): GEOAC_E_UNSUPPORTED with a message for a context holding an ensemble.  Weak: this file is also linked on its own against stand-ins
+// of the C ABI (the scheduler's thread-sanitizer test), which have no ensembles
+extern "C" int geoac_refuse_ensemble(geoac_ctx* ctx, const char* what) __attribute__((weak));
+
 extern "C" {
 
 int geoac_eig_default_params(geoac_eig_params* p){
@@ -981,11 +985,15 @@ int geoac_eig_default_params(geoac_eig_params* p){
     return 0;
 }
 int geoac_eig_search(geoac_ctx* ctx, const geoac_eig_params* p, int n_rcvr, const double* rcvr, geoac_eig_result** out){
+    if(geoac_refuse_ensemble)
+        if(int rc = geoac_refuse_ensemble(ctx, "eig_search")) return rc;
     return run_all(ctx, p, n_rcvr, rcvr, false, nullptr, nullptr, 0, out);
 }
 int geoac_eig_direct(geoac_ctx* ctx, const geoac_eig_params* p, int n_rcvr, const double* rcvr,
                      const double* theta_est, const double* phi_est, int bounces, geoac_eig_result** out){
     if(!theta_est || !phi_est || bounces < 0) return GEOAC_E_INVALID;
+    if(geoac_refuse_ensemble)
+        if(int rc = geoac_refuse_ensemble(ctx, "eig_direct")) return rc;
     return run_all(ctx, p, n_rcvr, rcvr, true, theta_est, phi_est, bounces, out);
 }
 int64_t geoac_eig_count(const geoac_eig_result* r){ return r ? (int64_t)(r->eig.size() / GEOAC_EIG_STRIDE) : 0; }

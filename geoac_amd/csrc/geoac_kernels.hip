@@ -310,6 +310,20 @@ DEVINL double rho_eval(const GeoacDevParams& P, int k, double x){
     return __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, q[3], q[2]), q[1]), q[0]);
 }
 
+// ensembles (geoac_device.h): the parameter block as a kernel of a single-profile fan with member m's profile would see it - m's tables and
+// reference state.  m is wave-uniform wherever a kernel derives it (readfirstlane: the pointers stay in scalar registers).
+DEVINL void member_view(GeoacDevParams& P, int m){
+    P.seg += (size_t)m * P.nseg * GEOAC_SEGW;
+    P.rho += (size_t)m * P.nseg * 4;
+    if(P.atab) P.atab += (size_t)m * (P.nseg + 2) * GEOAC_ATABW;
+    const double* c = P.mem_consts + (size_t)m * GEOAC_MEMC;
+    P.T_o = c[0]; P.P_o = c[1]; P.cbrt_To = c[2]; P.c000 = c[3];
+}
+DEVINL int member_of_slot(const GeoacDevParams& P, int slot){
+    const int m = __builtin_amdgcn_readfirstlane(slot) / P.mem_slots;
+    return m < P.n_members ? m : P.n_members - 1;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Global equation set: fused GeoAc_UpdateSources + GeoAc_EvalSrcEq (EquationSets.Global.cpp:222-442),
 // specialised for the stratified atmosphere (w = 0, every d/dlat, d/dlon of the medium = 0).
@@ -1725,10 +1739,11 @@ DEVINL void pp_exact(const GeoacDevParams& P, const double* aux, const double* A
 // ------------------------------------------------------------------------------------------------
 // k_init: launch angles -> initial conditions + per-ray state
 // ------------------------------------------------------------------------------------------------
-template <class EQ>
+template <class EQ, bool ENS = false>
 __global__ void __launch_bounds__(256) k_init(GeoacDevParams P){
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= P.n_pad) return;
+    if constexpr (ENS) member_view(P, member_of_slot(P, (int)(blockIdx.x * blockDim.x)));      // (S is a multiple of the workgroup)
     if(i == 0) EQ::fan_init(P);
     double* st = P.state + i;
     const size_t np = (size_t)P.n_pad;
@@ -1777,7 +1792,7 @@ DEVINL void write_row(const GeoacDevParams& P, double* p, int q, const double* y
     }
 }
 
-template <class EQ, bool LDS, bool SMP>
+template <class EQ, bool LDS, bool SMP, bool ENS = false>
 __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAVES : 1) k_rk4(GeoacDevParams P){
     constexpr int E = EQ::E;
     __builtin_amdgcn_s_setprio(3);      // latency-critical serial recurrence: win VALU arbitration against co-resident post-pass waves
@@ -1813,6 +1828,13 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
     const int q = tid % EQ::LANES;                              // pair kernel: which derivative system this lane carries; quad kernels: which cell corner
     const int qs = EQ::SPLIT ? (q >> EQ::SYS_SHIFT) : 0;        // split-state policies: the launch-angle system of this lane (eight-lane kernel: q >> 2)
     const int col_hi = P.colmap ? min(P.slot_hi, *P.n_cols) : P.slot_hi;
+    if constexpr (ENS){
+        // every workgroup integrates rays of one member (member-major slots; the compacted list pads each member's columns to whole
+        // workgroups): its first column names the member, whose table is then the one staged in LDS
+        static_assert(EQ::LANES == 1 && !EQ::COOP, "ensembles: one lane per ray, stratified sets");
+        const int c0 = P.slot_lo + (int)(bidx * blockDim.x);
+        member_view(P, member_of_slot(P, (P.colmap && c0 < col_hi) ? P.colmap[c0] : c0));
+    }
     const bool mine = !(P.spread > 1 && (tid0 & (P.spread - 1))) && col < col_hi;   // spread > 1: sparse lanes (grid sets, small fans)
     const int slot = (P.colmap && mine) ? P.colmap[col] : col;  // ray slot
     const size_t np = (size_t)P.n_pad;
@@ -2223,8 +2245,8 @@ DEVINL void pp_medium_by_key(const GeoacDevParams& P, char* wl, bool valid, unsi
     }
 }
 
-template <class EQ>
-__global__ void __launch_bounds__(256, EQ::PP_WAVES) k_postpass(GeoacDevParams P, int rows){
+template <class EQ, bool ENS = false>
+__global__ void __launch_bounds__(256, (ENS && EQ::PP_WAVES > 3) ? 3 : EQ::PP_WAVES) k_postpass(GeoacDevParams P, int rows){   // (ensembles: the member base pointers take two registers more)
     // grid-stride sweep over (segment row i, ray slot); by default the grid covers the sweep in one pass
     // Grid sets (PP_TILE): a workgroup takes a tile of 16 rows x 16 rays, a wave 16 consecutive rows of 4 rays.  The segment midpoints of
     // one ray's consecutive rows lie in the same cell and vertical segment nearly always, so the 64 lanes of a table gather touch a handful
@@ -2232,6 +2254,7 @@ __global__ void __launch_bounds__(256, EQ::PP_WAVES) k_postpass(GeoacDevParams P
     // rows are read in 32-byte pieces (16 lines per load) that the four waves of the workgroup share.
     const size_t np = (size_t)P.n_pad;
     const int bx = EQ::PP_TILE ? (P.n_cols_bound + 15) / 16 : (P.n_cols_bound + 255) / 256;      // column-blocks per row (tile row)
+    const double* const seg0 = P.seg; const double* const rho0 = P.rho;      // (ensembles: the member tables' base)
     const long long total = (long long)bx * (EQ::PP_TILE ? (rows - 1 + 15) / 16 : rows - 1);
     for(long long w = blockIdx.x; w < total; w += gridDim.x){
         const int i = EQ::PP_TILE ? (int)(w / bx) * 16 + (int)((threadIdx.x & 63u) >> 2) : (int)(w / bx);
@@ -2281,6 +2304,10 @@ __global__ void __launch_bounds__(256, EQ::PP_WAVES) k_postpass(GeoacDevParams P
         const double* b = a + (size_t)EQ::PW * np;
         double* o = P.contrib + ((size_t)i * 2) * np + col;
         double tt, at;
+        if constexpr (ENS){                                       // (a wave's columns belong to one member; the block is viewed in place - a copy would go to scratch)
+            P.seg = seg0; P.rho = rho0;
+            member_view(P, member_of_slot(P, slot));
+        }
         EQ::segment(P, P.state + slot, np, a, b, tt, at);
         o[0]  = tt;
         o[np] = at;
@@ -2301,7 +2328,7 @@ __global__ void __launch_bounds__(256, EQ::PP_WAVES) k_postpass(GeoacDevParams P
 // workgroup, conflict-free), not in 38 registers, and no row is prefetched - with it the kernel fits 128 registers: FOUR waves per SIMD, whose
 // loads cover one another's latency (config 3's post-pass waited in 53 % of its wave cycles at two waves per SIMD).  Same operations on the
 // same operands: same bits.
-template <class EQ, bool ONETRIP, bool TBL = false>
+template <class EQ, bool ONETRIP, bool TBL = false, bool ENS = false>
 __global__ void __launch_bounds__(256, (EQ::PW == 6 && !TBL) ? GEOAC_PPTAB_GLOBAL_WAVES : 4) k_postpass_tab(GeoacDevParams P, int rows, int gy0){
     constexpr int PW = EQ::PW, R = GEOAC_PP_ROWS;
     extern __shared__ double pp_tb_lds[];
@@ -2317,6 +2344,7 @@ __global__ void __launch_bounds__(256, (EQ::PW == 6 && !TBL) ? GEOAC_PPTAB_GLOBA
     if(col >= ncol) return;
     const int nr = P.nrows[col];
     const int slot = P.colmap ? P.colmap[col] : col;
+    if constexpr (ENS) member_view(P, member_of_slot(P, slot));      // (a wave's columns belong to one member)
     double aux[2] = { 0.0, 0.0 };
     EQ::pp_aux(P, P.state + slot, np, aux);
     {   // grid: x = blocks of 256 columns, y = groups of R rows, from group gy0 on (the host cuts a launch at the grid's y limit)
@@ -2430,7 +2458,7 @@ __global__ void __launch_bounds__(256, (EQ::PW == 6 && !TBL) ? GEOAC_PPTAB_GLOBA
 
 // k_ppfix: the segments k_postpass_tab listed (the table did not serve them: a flagged entry, a midpoint beyond the strips) - attenuation by
 // the exact routine, as k_postpass computes it, with the segment geometry of k_postpass_tab.  One thread per list entry; usually none.
-template <class EQ>
+template <class EQ, bool ENS = false>
 __global__ void __launch_bounds__(256) k_ppfix(GeoacDevParams P){
     constexpr int PW = EQ::PW;
     const size_t np = (size_t)P.n_pad;
@@ -2439,20 +2467,22 @@ __global__ void __launch_bounds__(256) k_ppfix(GeoacDevParams P){
     for(unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (unsigned long long)gridDim.x * blockDim.x){
         const int col = P.ppfix[2 * q], i = P.ppfix[2 * q + 1];
         const int slot = P.colmap ? P.colmap[col] : col;
+        GeoacDevParams Pm = P;                                    // ensembles: the entries are any columns - a member per lane (rare work)
+        if constexpr (ENS){ const int m = slot / P.mem_slots; member_view(Pm, m < P.n_members ? m : P.n_members - 1); }
         double aux[2] = { 0.0, 0.0 };
-        EQ::pp_aux(P, P.state + slot, np, aux);
+        EQ::pp_aux(Pm, P.state + slot, np, aux);
         const double* a = P.path + ((size_t)i * PW) * np + col;
         double A[PW], B[PW];
         #pragma unroll
         for(int c = 0; c < PW; c++){ A[c] = a[(size_t)c * np]; B[c] = a[(size_t)(PW + c) * np]; }
         double ref[3] = { 0.15915494309189532, 0.0, 1.0 };
         PPGeom G;
-        EQ::pp_geom(P, aux, A, B, G, ref);
+        EQ::pp_geom(Pm, aux, A, B, G, ref);
         const double xe = clampq(G.x, P.x_min, P.x_max);
-        const int k = seg_find(P.seg, P.nseg, xe, (int)((xe - P.x_min) * P.seg_per_x));
-        double T, u, v; seg_eval_f(P.seg + (size_t)k * GEOAC_SEGW, xe, T, u, v);
+        const int k = seg_find(Pm.seg, P.nseg, xe, (int)((xe - P.x_min) * P.seg_per_x));
+        double T, u, v; seg_eval_f(Pm.seg + (size_t)k * GEOAC_SEGW, xe, T, u, v);
         const double qT = kGamR * T;
-        P.contrib[((size_t)i * 2 + 1) * np + col] = suthbass_alpha(P, G.x - P.r_earth, qT * frsq(qT), rho_eval(P, k, xe), P.freq, P.T_o, P.P_o, P.cbrt_To) * G.ds_at;
+        P.contrib[((size_t)i * 2 + 1) * np + col] = suthbass_alpha(Pm, G.x - P.r_earth, qT * frsq(qT), rho_eval(Pm, k, xe), P.freq, Pm.T_o, Pm.P_o, Pm.cbrt_To) * G.ds_at;
     }
 }
 
@@ -2533,12 +2563,20 @@ __global__ void __launch_bounds__(64) k_atab_build(GeoacDevParams P, double* __r
 // k_arrival: the arrival part of the records (GeoAcGlobal_main.cpp:296-317 and twins) from the leg's last row, which
 // k_rk4 left in the record.  One thread per (ray, leg); runs once, behind the fan's last RK4 launch.
 // ------------------------------------------------------------------------------------------------
-template <class EQ>
+template <class EQ, bool ENS = false>
 __global__ void __launch_bounds__(256) k_arrival(GeoacDevParams P){
     const int legs = P.bounces + 1;
     const long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    int slot, leg;
+    if constexpr (ENS){                                           // grid y = member: the (slot, leg) pairs of member y's slot range
+        if(id >= (long long)P.mem_slots * legs) return;
+        member_view(P, (int)blockIdx.y);
+        slot = (int)blockIdx.y * P.mem_slots + (int)(id / legs); leg = (int)(id % legs);
+        if(P.perm[slot] < 0) return;                              // (slots without a ray)
+    } else {
     if(id >= (long long)P.n_rays * legs) return;
-    const int slot = (int)(id / legs), leg = (int)(id % legs);
+    slot = (int)(id / legs); leg = (int)(id % legs);
+    }
     double* R = P.rec + ((size_t)(P.perm ? P.perm[slot] : slot) * legs + leg) * GEOAC_REC_STRIDE;
     if(R[GEOAC_REC_VALID] == 0.0) return;
     const size_t np = (size_t)P.n_pad;
@@ -2694,6 +2732,46 @@ __global__ void __launch_bounds__(1024) k_compact(GeoacDevParams P, const int* _
     if(threadIdx.x == 0) *n_next = base_s;
 }
 
+// k_compact_ens: k_compact for ensembles, segmented by member.  Member m's live columns are packed in order into a range that starts where
+// member m - 1's ended and is padded up to a multiple of `align` (the RK4 workgroup width), so that no workgroup holds rays of two members;
+// a padding column names the member's last slot, which never carries a ray (a finished ray to every kernel).  The K + 1 range starts of the
+// list are stored behind it (next[n_pad + m]) for the next compaction; the first one (cur == NULL) walks the member slot ranges.
+__global__ void __launch_bounds__(1024) k_compact_ens(GeoacDevParams P, const int* __restrict__ cur, const int* __restrict__ n_cur,
+                                                      int* __restrict__ next, int* __restrict__ n_next, int align){
+    __shared__ int wave_cnt[16];
+    __shared__ int base_s;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t np = (size_t)P.n_pad;
+    const int S = P.mem_slots;
+    if(threadIdx.x == 0) base_s = 0;
+    __syncthreads();
+    for(int m = 0; m < P.n_members; m++){
+        const int lo = cur ? cur[np + m] : m * S;
+        const int hi = cur ? (m + 1 < P.n_members ? cur[np + m + 1] : *n_cur) : (m + 1) * S;
+        if(threadIdx.x == 0) next[np + m] = base_s;
+        for(int t0 = lo; t0 < hi; t0 += 1024){
+            const int c = t0 + threadIdx.x;
+            const int slot = (c < hi) ? (cur ? cur[c] : c) : -1;
+            const bool live = slot >= 0 && P.state[ST_DONE * np + slot] == 0.0;
+            const unsigned long long mk = __ballot(live);
+            if(lane == 0) wave_cnt[wv] = __popcll(mk);
+            __syncthreads();
+            int off = base_s;
+            for(int w = 0; w < wv; w++) off += wave_cnt[w];
+            if(live) next[off + __popcll(mk & ((1ull << lane) - 1ull))] = slot;
+            __syncthreads();
+            if(threadIdx.x == 0){ int tot = 0; for(int w = 0; w < 16; w++) tot += wave_cnt[w]; base_s += tot; }
+            __syncthreads();
+        }
+        const int end = base_s, end_pad = (end + align - 1) / align * align;
+        for(int c = end + (int)threadIdx.x; c < end_pad; c += 1024) next[c] = (m + 1) * S - 1;
+        __syncthreads();
+        if(threadIdx.x == 0) base_s = end_pad;
+        __syncthreads();
+    }
+    if(threadIdx.x == 0) *n_next = base_s;
+}
+
 // ------------------------------------------------------------------------------------------------
 // device-function probes (include/geoac_probe.h): one thread per point through the very functions the RK4 and post-pass kernels call,
 // so that the table lookups and the absorption model have parity tests of their own (not only through fan integrals)
@@ -2772,6 +2850,21 @@ __global__ void __launch_bounds__(64) k_probe_grid(GeoacDevParams P, int n, cons
 // host-callable launchers (called from geoac_api.cpp)
 // ------------------------------------------------------------------------------------------------
 #ifndef GEOAC_NO_LAUNCHERS          // tools/dev_kernel.sh compiles single instantiations of the kernels above
+// ensembles: the stratified sets only (one-lane policies)
+#define GEOAC_DISPATCH_EQ_ENS(P, CALL) \
+    switch((P)->eqset * 2 + ((P)->calc_amp ? 1 : 0)){ \
+        case GEOAC_EQ_GLOBAL * 2 + 1: { using EQ = EqGlobal<true>;  CALL; } break; \
+        case GEOAC_EQ_GLOBAL * 2 + 0: { using EQ = EqGlobal<false>; CALL; } break; \
+        case GEOAC_EQ_3D * 2 + 1:     { using EQ = Eq3D<true>;      CALL; } break; \
+        case GEOAC_EQ_3D * 2 + 0:     { using EQ = Eq3D<false>;     CALL; } break; \
+        case GEOAC_EQ_2D * 2 + 1:     { using EQ = Eq2D<true>;      CALL; } break; \
+        case GEOAC_EQ_2D * 2 + 0:     { using EQ = Eq2D<false>;     CALL; } break; \
+        default: return hipErrorNotSupported; }
+template <class EQ> struct IsStrat { static constexpr bool v = false; };
+template <bool A> struct IsStrat<EqGlobal<A>> { static constexpr bool v = true; };
+template <bool A> struct IsStrat<Eq3D<A>> { static constexpr bool v = true; };
+template <bool A> struct IsStrat<Eq2D<A>> { static constexpr bool v = true; };
+
 #define GEOAC_DISPATCH_EQ(P, CALL) \
     switch((P)->eqset * 2 + ((P)->calc_amp ? 1 : 0)){ \
         case GEOAC_EQ_GLOBAL * 2 + 1: { using EQ = EqGlobal<true>;  CALL; } break; \
@@ -2841,6 +2934,7 @@ __global__ void __launch_bounds__(64) k_probe_grid(GeoacDevParams P, int n, cons
 
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s){
     dim3 b(256), g((P->n_pad + 255) / 256);
+    if(P->n_members > 1){ GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_init<EQ, true>), g, b, 0, s, *P)); return hipGetLastError(); }
     GEOAC_DISPATCH_EQ(P, hipLaunchKernelGGL(k_init<EQ>, g, b, 0, s, *P));
     return hipGetLastError();
 }
@@ -2867,12 +2961,21 @@ static hipError_t launch_rk4_t(const GeoacDevParams* P, int block, hipStream_t s
     }
     const bool smp = (P->mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)) != 0;
     if(smp && EQ::SPLIT && !EQ::ROW_SPLIT) return hipErrorNotSupported;                  // (the eight-lane kernel has no sample capture)
-    #define GEOAC_RK4_LAUNCH(LDSF, SMPF) do { \
+    #define GEOAC_RK4_LAUNCH(LDSF, SMPF, ...) do { \
         if(lds > 65536){ \
-            hipError_t err = hipFuncSetAttribute((const void*)k_rk4<EQ, LDSF, SMPF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+            hipError_t err = hipFuncSetAttribute((const void*)k_rk4<EQ, LDSF, SMPF __VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
             if(err != hipSuccess) return err; \
         } \
-        hipLaunchKernelGGL((k_rk4<EQ, LDSF, SMPF>), g, b, lds, s, *P); } while(0)
+        hipLaunchKernelGGL((k_rk4<EQ, LDSF, SMPF __VA_ARGS__>), g, b, lds, s, *P); } while(0)
+    if(P->n_members > 1){
+        // ensembles (arrivals only, one lane per ray): workgroups must not straddle two members' slot ranges / compacted column ranges
+        if constexpr (IsStrat<EQ>::v){
+            if(smp || (P->mem_slots % block) != 0 || (P->slot_lo % block) != 0) return hipErrorInvalidValue;
+            if(P->table_in_lds) GEOAC_RK4_LAUNCH(true, false, , true); else GEOAC_RK4_LAUNCH(false, false, , true);
+            return hipGetLastError();
+        }
+        return hipErrorNotSupported;
+    }
     if(P->table_in_lds){ if(smp) GEOAC_RK4_LAUNCH(true, true); else GEOAC_RK4_LAUNCH(true, false); }
     else               { if(smp) GEOAC_RK4_LAUNCH(false, true); else GEOAC_RK4_LAUNCH(false, false); }
     #undef GEOAC_RK4_LAUNCH
@@ -2937,6 +3040,10 @@ static hipError_t launch_rk4_duo(const GeoacDevParams*, hipStream_t, unsigned*){
 static hipError_t launch_rk4_trio(const GeoacDevParams*, hipStream_t, unsigned*){ return hipErrorNotSupported; }
 #endif
 extern "C" hipError_t geoac_launch_rk4(const GeoacDevParams* P, int block, hipStream_t s, unsigned* n_wg){
+    if(P->n_members > 1){
+        if(P->duo || P->trio || P->lanes_per_ray != 1 || P->gtab) return hipErrorNotSupported;
+        GEOAC_DISPATCH_EQ_ENS(P, return launch_rk4_t<EQ>(P, block, s, n_wg));
+    }
     if(P->duo) return launch_rk4_duo(P, s, n_wg);
     if(P->trio && P->lanes_per_ray == 2 && !P->gtab && P->eqset == GEOAC_EQ_GLOBAL) return launch_rk4_trio(P, s, n_wg);
     if(P->lanes_per_ray == 2 && !P->gtab && P->eqset == GEOAC_EQ_GLOBAL) return launch_rk4_t<EqGlobalPair>(P, block, s, n_wg);
@@ -2972,6 +3079,7 @@ extern "C" hipError_t geoac_launch_postpass(const GeoacDevParams* P, int rows, h
     if(nbl > 0x7fffffffLL) nbl = 0x7fffffffLL;
     int nb = (int)nbl;
     dim3 b(256), g(nb);
+    if(P->n_members > 1){ GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_postpass<EQ, true>), g, b, 0, s, *P, rows)); return hipGetLastError(); }
     GEOAC_DISPATCH_EQ(P, hipLaunchKernelGGL(k_postpass<EQ>, g, b, EQ::PP_DEDUP ? 4 * GEOAC_PP_SLOTS * GEOAC_PP_SLOTB : 0, s, *P, rows));
     return hipGetLastError();
 }
@@ -2991,6 +3099,20 @@ extern "C" hipError_t geoac_launch_postpass_tab(const GeoacDevParams* P, int row
     unsigned pad = (unsigned)P->pp_lds_pad;
     int v = (P->eqset * 2 + (P->calc_amp ? 1 : 0)) * 2 + (P->pp_onetrip ? 1 : 0);
     void (*f)(GeoacDevParams, int, int) = nullptr;
+    const bool ens = P->n_members > 1;
+    if(ens){
+        // ensembles: the one-trip form (the plan of the fans that fill the chip), a member per wave
+        switch(P->eqset * 2 + (P->calc_amp ? 1 : 0)){
+            case GEOAC_EQ_GLOBAL * 2 + 1: f = k_postpass_tab<EqGlobal<true>, true, false, true>; break;
+            case GEOAC_EQ_GLOBAL * 2 + 0: f = k_postpass_tab<EqGlobal<false>, true, false, true>; break;
+            case GEOAC_EQ_3D * 2 + 1:     f = k_postpass_tab<Eq3D<true>, true, false, true>; break;
+            case GEOAC_EQ_3D * 2 + 0:     f = k_postpass_tab<Eq3D<false>, true, false, true>; break;
+            case GEOAC_EQ_2D * 2 + 1:     f = k_postpass_tab<Eq2D<true>, true, false, true>; break;
+            case GEOAC_EQ_2D * 2 + 0:     f = k_postpass_tab<Eq2D<false>, true, false, true>; break;
+            default: return hipErrorNotSupported;
+        }
+        v = 26 + P->eqset * 2 + (P->calc_amp ? 1 : 0);
+    } else
     if(P->pp_lds_table && P->eqset == GEOAC_EQ_GLOBAL && P->pp_onetrip){
         // the table entry in LDS (19 x 256 doubles per workgroup), four waves per SIMD: the fans of the spherical set that fill the chip
         f = P->calc_amp ? k_postpass_tab<EqGlobal<true>, true, true> : k_postpass_tab<EqGlobal<false>, true, true>;
@@ -3030,6 +3152,7 @@ extern "C" hipError_t geoac_launch_postpass_tab(const GeoacDevParams* P, int row
     if(e != hipSuccess) return e;
     // the listed segments, exactly (the list's counter was zeroed on this stream before the launch above: geoac_api.cpp)
     dim3 gf(64);
+    if(ens){ GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_ppfix<EQ, true>), gf, b, 0, s, *P)); return hipGetLastError(); }
     switch(P->eqset * 2 + (P->calc_amp ? 1 : 0)){
         case GEOAC_EQ_GLOBAL * 2 + 1: hipLaunchKernelGGL(k_ppfix<EqGlobal<true>>, gf, b, 0, s, *P); break;
         case GEOAC_EQ_GLOBAL * 2 + 0: hipLaunchKernelGGL(k_ppfix<EqGlobal<false>>, gf, b, 0, s, *P); break;
@@ -3069,7 +3192,13 @@ extern "C" hipError_t geoac_launch_probe_grid(const GeoacDevParams* P, int n, co
     return hipGetLastError();
 }
 
-extern "C" hipError_t geoac_launch_compact(const GeoacDevParams* P, const int* cur, const int* n_cur, int n_first, int* next, int* n_next, hipStream_t s){
+extern "C" hipError_t geoac_launch_compact(const GeoacDevParams* P, const int* cur, const int* n_cur, int n_first, int* next, int* n_next, int align, hipStream_t s){
+    if(P->n_members > 1){
+        // (next, cur: n_pad + n_members ints - the list, then the members' range starts)
+        if(align < 64 || (P->mem_slots % align) != 0) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(k_compact_ens, dim3(1), dim3(1024), 0, s, *P, cur, n_cur, next, n_next, align);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(1024), 0, s, *P, cur, n_cur, n_first, next, n_next);
     return hipGetLastError();
 }
@@ -3077,6 +3206,12 @@ extern "C" hipError_t geoac_launch_compact(const GeoacDevParams* P, const int* c
 extern "C" hipError_t geoac_launch_arrival(const GeoacDevParams* P, hipStream_t s){
     dim3 b(256), g((unsigned)(((long long)P->n_rays * (P->bounces + 1) + 255) / 256));
     const bool amp = P->calc_amp != 0;
+    if(P->n_members > 1){
+        if(!P->perm) return hipErrorInvalidValue;
+        dim3 ge((unsigned)(((long long)P->mem_slots * (P->bounces + 1) + 255) / 256), (unsigned)P->n_members);
+        GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_arrival<EQ, true>), ge, b, 0, s, *P));
+        return hipGetLastError();
+    }
     switch(P->eqset){
         case GEOAC_EQ_GLOBAL: if(amp) hipLaunchKernelGGL(k_arrival<EqGlobal<true>>, g, b, 0, s, *P); else hipLaunchKernelGGL(k_arrival<EqGlobal<false>>, g, b, 0, s, *P); break;
         case GEOAC_EQ_3D:     if(amp) hipLaunchKernelGGL(k_arrival<Eq3D<true>>, g, b, 0, s, *P);     else hipLaunchKernelGGL(k_arrival<Eq3D<false>>, g, b, 0, s, *P); break;

@@ -133,6 +133,20 @@ int  geoac_set_stream(geoac_ctx* ctx, void* hip_stream);
 int  geoac_upload_atmo_1d(geoac_ctx* ctx, int n, const double* x, const double* T, const double* u,
                           const double* v, const double* rho, const double* slopes4);
 
+/* ensemble of K stratified profiles on the shared nodes x (GEOAC_EQ_2D, GEOAC_EQ_3D, GEOAC_EQ_GLOBAL; 1 <= K <= GEOAC_MAX_MEMBERS): T, u, v, rho
+ * [K][n], slopes4 [K][4*n] in the per-member layout of geoac_upload_atmo_1d.  One geoac_fan_launch then integrates the fan's angles through
+ * every member; member m's records are bit-identical to those of a context loaded with profile m alone.  Once K > 1:
+ *   - geoac_fan_fetch, geoac_fan_records_dev and geoac_fan_copy_records_dev cover [K][n_rays][legs][GEOAC_REC_STRIDE], member-major;
+ *   - total_steps is the sum over the members, geoac_abs_table_info sums over the members' tables;
+ *   - geoac_medium_1d and the device-function probes (geoac_probe.h) evaluate member 0;
+ *   - sample capture (GEOAC_MODE_WRITE_RAYS / _CAUSTICS), the eigenray searches, geoac_clone and the pool return GEOAC_E_UNSUPPORTED.
+ * geoac_upload_atmo_1d sets K back to 1.  A range-dependent set returns GEOAC_E_UNSUPPORTED. */
+#define GEOAC_MAX_MEMBERS 64
+int  geoac_upload_atmo_1d_ensemble(geoac_ctx* ctx, int n_members, int n, const double* x, const double* T, const double* u,
+                                   const double* v, const double* rho, const double* slopes4);
+/* K of the uploaded atmosphere (1 unless an ensemble was uploaded) */
+int  geoac_get_members(geoac_ctx* ctx, int* n_members);
+
 /* range-dependent Cartesian atmosphere (GEOAC_EQ_3D_RNGDEP): nx x ny profiles of nz nodes on common z nodes;
  * fields are [nx][ny][nz] row-major (T [K], u,v [km/s, tapered], rho).  Replaces Spline_Multi_G2S + Set_Slopes_Multi
  * (G2S_MultiDimSpline3D.cpp:306-425, 1603-1621): vertical natural splines of f, df/dx, df/dy per node are built here.

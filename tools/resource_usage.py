@@ -46,7 +46,7 @@ def main():
             if args and not any(a in r["name"] for a in args):
                 continue
             print(f'{r["name"]:<70s} VGPR {r.get("VGPRs", "?"):>3s} AGPR {r.get("AGPRs", "?"):>3s} spillV {r.get("VGPRs Spill", "?"):>3s} spillS {r.get("SGPRs Spill", "?"):>3s} '
-                  f'scratch {r.get("ScratchSize", "?"):>4s} occ {r.get("Occupancy", "?")}')
+                  f'scratch {r.get("ScratchSize", "?"):>4s} occ {r.get("Occupancy", "?")} LDS {r.get("LDS Size", "?")}')
             if fail_pat and re.search(fail_pat, r["name"]) and int(r.get("ScratchSize", "0")) > 0:
                 bad += 1
     if bad:
