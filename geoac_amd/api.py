@@ -192,6 +192,7 @@ class FanContext:
         self.params = default_params(eqset)
         self.n_rays = 0
         self.n_members = 1
+        self.n_sources = 1
 
     def _chk(self, rc):
         if rc:
@@ -218,6 +219,7 @@ class FanContext:
         c.params = Params.from_buffer_copy(bytes(self.params))
         c.n_rays = 0
         c.n_members = 1
+        c.n_sources = 1
         if hasattr(self, "_grid_dims"):
             c._grid_dims = self._grid_dims
         return c
@@ -301,6 +303,17 @@ class FanContext:
                 setattr(self.params, k, val)
         self._chk(self.lib.geoac_set_params(self._h, ctypes.byref(self.params)))
 
+    def set_sources(self, src):
+        """source set (geoac_set_sources): src [n_src][3], each row in the layout of Params.src.  One launch then integrates the fan's angles from
+        every source (and through every profile of an ensemble): fetch() / run() return (n_src, n_rays, legs, 32), or (n_src, K, n_rays, legs, 32)
+        with an ensemble of K; rec[s] is bit-identical to a run with set_params(src=src[s]).  One row sets Params.src and leaves the mode."""
+        src = _arr(src)
+        if src.ndim != 2 or src.shape[1] != 3 or src.shape[0] < 1:
+            raise GeoAcError(f"set_sources: src must be an array of shape [n_src][3] with n_src >= 1 (got {src.shape})")
+        self._chk(self.lib.geoac_set_sources(self._h, src.shape[0], _p(src)))
+        self.n_sources = src.shape[0]
+        self.params.src = (ctypes.c_double * 3)(*src[0])
+
     def set_angles(self, theta_deg, phi_deg):
         th, ph = _arr(theta_deg), _arr(phi_deg)
         if th.ndim != 1 or th.shape != ph.shape:
@@ -313,9 +326,14 @@ class FanContext:
 
     def fetch(self, out=None):
         """records of the last launch; `out`: caller-owned C-contiguous float64 array [n_rays][legs][32] (e.g. the numpy view of a pinned
-        torch tensor) to copy into instead of a fresh array.  Ensembles (n_members > 1): [K][n_rays][legs][32]"""
+        torch tensor) to copy into instead of a fresh array.  Ensembles (n_members > 1): [K][n_rays][legs][32]; source sets (n_sources > 1):
+        [n_src][n_rays][legs][32], with an ensemble [n_src][K][n_rays][legs][32]"""
         legs = self.params.bounces + 1
-        shape = (self.n_rays, legs, REC_STRIDE) if self.n_members == 1 else (self.n_members, self.n_rays, legs, REC_STRIDE)
+        shape = (self.n_rays, legs, REC_STRIDE)
+        if self.n_members > 1:
+            shape = (self.n_members,) + shape
+        if self.n_sources > 1:
+            shape = (self.n_sources,) + shape
         if out is None:
             rec = np.empty(shape)
         else:

@@ -202,8 +202,12 @@ struct geoac_ctx {
     int n_members = 1;
     int mem_slots = 0;                            // ray slots per member of the current angle layout (K > 1)
     std::vector<double> ens_T, ens_rho, ens_sl;
-    std::vector<double> mconsts;                  // [K][GEOAC_MEMC] of the last launch
-    DevBuf d_mconsts;
+    std::vector<double> mconsts;                  // [K][GEOAC_MEMP] of the last launch
+    DevBuf d_mconsts;                             // [n_src K][GEOAC_MEMC]: the members' profile state and source (GeoacDevParams::mem_consts)
+    // source sets (geoac_set_sources): the fan from n_src source points in one launch; a member of the launch is a (source, profile) pair, m = s K + k
+    int n_src = 1;
+    std::vector<double> sources;                  // [n_src][3] while n_src > 1 (prm.src holds source 0)
+    int layout_members = 1;                       // n_src K the slot layout was built for
     std::vector<double> ang_th, ang_ph;           // the caller's launch angles (the slot layout is rebuilt when K changes)
     std::string err;
 };
@@ -429,6 +433,7 @@ int geoac_clone(geoac_ctx* src, geoac_ctx** out){
     if(!src || !out) return GEOAC_E_INVALID;
     if(!src->have_atmo) return fail(src, GEOAC_E_INVALID, "clone: no atmosphere uploaded");
     if(src->n_members > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
+    if(src->n_src > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a source set is active (geoac_set_sources); set a single source first");
     geoac_ctx* c = nullptr;
     int rc = geoac_create(&c, src->eqset, src->device);
     if(rc) return rc;
@@ -496,7 +501,7 @@ static int upload_members(geoac_ctx* ctx, int K, int n, const double* x, const d
     ctx->n_members = K;
     if(K > 1){ ctx->ens_T.assign(T, T + K * nn); ctx->ens_rho.assign(rho, rho + K * nn); ctx->ens_sl.assign(slopes4, slopes4 + 4 * nn * K); }
     else { ctx->ens_T.clear(); ctx->ens_rho.clear(); ctx->ens_sl.clear(); }
-    if(K != K_was && ctx->have_angles) return layout_angles(ctx);       // (the slot layout depends on K)
+    if(K != K_was && ctx->have_angles) return layout_angles(ctx);       // (the slot layout depends on K, and on the sources)
     return GEOAC_OK;
 }
 
@@ -524,13 +529,36 @@ int geoac_upload_atmo_1d_ensemble(geoac_ctx* ctx, int n_members, int n, const do
 
 // the callers inside the library that take one profile per context (eigenray searches, the pool): GEOAC_E_UNSUPPORTED with a message for an ensemble
 int geoac_refuse_ensemble(geoac_ctx* ctx, const char* what){
-    if(!ctx || ctx->n_members <= 1) return GEOAC_OK;
+    if(!ctx) return GEOAC_OK;
+    if(ctx->n_src > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a source set is active (geoac_set_sources); set a single source first");
+    if(ctx->n_members <= 1) return GEOAC_OK;
     return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
 }
 
 int geoac_get_members(geoac_ctx* ctx, int* n_members){
     if(!ctx || !n_members) return fail(ctx, GEOAC_E_INVALID, "get_members: bad arguments");
     *n_members = ctx->n_members;
+    return GEOAC_OK;
+}
+
+int geoac_set_sources(geoac_ctx* ctx, int n_src, const double* src){
+    if(!ctx) return GEOAC_E_INVALID;
+    if(n_src < 1 || !src) return fail(ctx, GEOAC_E_INVALID, "set_sources: n_src must be at least 1 and src not NULL");
+    if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "set_sources: source sets are available for the stratified equation sets only");
+    if((long long)n_src * ctx->n_members > GEOAC_MAX_MEMBERS)
+        return fail(ctx, GEOAC_E_INVALID, "set_sources: " + std::to_string(n_src) + " sources x " + std::to_string(ctx->n_members) + " profiles exceed the " +
+                    std::to_string(GEOAC_MAX_MEMBERS) + " members of a launch");
+    ctx->prm.src[0] = src[0]; ctx->prm.src[1] = src[1]; ctx->prm.src[2] = src[2];
+    ctx->n_src = n_src;
+    if(n_src > 1) ctx->sources.assign(src, src + 3 * (size_t)n_src); else ctx->sources.clear();
+    if(ctx->have_angles && ctx->layout_members != n_src * ctx->n_members) return layout_angles(ctx);       // (the slot layout depends on the number of members)
+    return GEOAC_OK;
+}
+
+int geoac_get_sources(geoac_ctx* ctx, int* n_src){
+    if(!ctx || !n_src) return fail(ctx, GEOAC_E_INVALID, "get_sources: bad arguments");
+    *n_src = ctx->n_src;
     return GEOAC_OK;
 }
 
@@ -630,6 +658,7 @@ int geoac_set_params(geoac_ctx* ctx, const geoac_params* p){
     if(p->bounces < 0 || p->bounces + 1 > GEOAC_MAXLEGS) return fail(ctx, GEOAC_E_INVALID, "bounces out of range (0..63)");
     if(!(p->ds_min > 0) || !(p->ds_max >= p->ds_min)) return fail(ctx, GEOAC_E_INVALID, "ds_min/ds_max");
     ctx->prm = *p;
+    if(ctx->n_src > 1){ ctx->prm.src[0] = ctx->sources[0]; ctx->prm.src[1] = ctx->sources[1]; ctx->prm.src[2] = ctx->sources[2]; }      // (a source set stays; source 0 is what geoac_get_params reports)
     if(!(ctx->prm.vert_limit == ctx->prm.vert_limit) && ctx->have_atmo) ctx->prm.vert_limit = ctx->x[ctx->n_nodes - 1];
     if(ctx->have_grid){
         const double ext[4] = { ctx->gx.front(), ctx->gx.back(), ctx->gy.front(), ctx->gy.back() };
@@ -714,10 +743,12 @@ static int layout_angles(geoac_ctx* ctx){
         ctx->have_perm = true;
     }
     std::vector<int> eo; std::vector<double> et, ep;
-    if(ctx->n_members > 1){
-        // ensembles: member m owns the slots [m S, (m+1) S), each a copy of the single fan's layout; S: a multiple of the widest RK4 workgroup
+    ctx->layout_members = ctx->n_src * ctx->n_members;
+    if(ctx->layout_members > GEOAC_MAX_MEMBERS) ctx->layout_members = 0;      // (an ensemble upload behind geoac_set_sources: the launch refuses; no layout until the numbers fit)
+    if(ctx->layout_members > 1){
+        // ensembles and source sets: member m owns the slots [m S, (m+1) S), each a copy of the single fan's layout; S: a multiple of the widest RK4 workgroup
         // with at least one slot without a ray (the padding columns of the segmented compaction name it)
-        const int K = ctx->n_members, S = (n_rays + 1 + 255) / 256 * 256;
+        const int K = ctx->layout_members, S = (n_rays + 1 + 255) / 256 * 256;
         eo.assign((size_t)K * S, -1); et.assign((size_t)K * S, 0.0); ep.assign((size_t)K * S, 0.0);
         for(int m = 0; m < K; m++)
             for(int j = 0; j < n_rays; j++){
@@ -748,14 +779,22 @@ static int fan_launch_once(geoac_ctx* ctx){
     if(is_grid != ctx->have_grid) return fail(ctx, GEOAC_E_INVALID, "fan_launch: atmosphere kind does not match the equation set");
     HIPCHK(hipSetDevice(ctx->device));
     const geoac_params& p = ctx->prm;
-    const int K = ctx->n_members;
-    const bool ens = K > 1;
+    const int K = ctx->n_members;                 // profiles
+    const int n_src = ctx->n_src;
+    if((long long)n_src * K > GEOAC_MAX_MEMBERS)      // (checked in geoac_set_sources; an ensemble upload may have changed K since)
+        return fail(ctx, GEOAC_E_INVALID, "fan_launch: " + std::to_string(n_src) + " sources x " + std::to_string(K) + " profiles exceed the " +
+                    std::to_string(GEOAC_MAX_MEMBERS) + " members of a launch");
+    const int M = n_src * K;                      // members of the launch: (source, profile) pairs, m = s K + k
+    const bool ens = M > 1;
+    if(ctx->layout_members != M){ int rc = layout_angles(ctx); if(rc) return rc; }
+    if(n_src > 1 && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available while a source set is active; run the source on a context of its own");
     if(ens && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
         return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available for an ensemble; run the member on a context of its own");
     GeoacDevParams P{};
     P.eqset = ctx->eqset; P.calc_amp = p.calc_amp ? 1 : 0; P.mode = p.mode; P.bounces = p.bounces;
-    P.n_rays = ctx->n_rays * K; P.n_pad = ctx->n_pad;
-    P.n_members = K; P.mem_slots = ens ? ctx->mem_slots : 0; P.mem_consts = nullptr;
+    P.n_rays = ctx->n_rays * M; P.n_pad = ctx->n_pad;
+    P.n_members = M; P.n_profiles = K; P.mem_slots = ens ? ctx->mem_slots : 0; P.mem_consts = nullptr;
     const bool is_global = (ctx->eqset == GEOAC_EQ_GLOBAL);                                  // stratified spherical set (pair kernel, range test)
     const bool is_sph = is_global || ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP;                   // geocentric radius as the height coordinate
     if(is_global){ P.E = p.calc_amp ? 18 : 6; P.pathw = 6; }
@@ -786,16 +825,18 @@ static int fan_launch_once(geoac_ctx* ctx){
         // altitude as a radius, which clamps to the lowest node; the Cartesian twin evaluates at z = z_grnd)
         P.sb_const[0] = pow(10.0, -0.67887); P.sb_const[1] = pow(10.0, -0.10744); P.sb_const[2] = pow(10, -3.3979);
         P.sb_const[3] = 5.0 / sqrt(21.0); P.sb_const[4] = sqrt(3.0 / 7.0);
+        P.src_trig[0] = sin(p.src[1] * kPi / 180.0); P.src_trig[1] = cos(p.src[1] * kPi / 180.0);
         if(is_grid){ P.T_o = P.P_o = 0.0; P.c000 = 0.0; } else {
         // (ensembles: per member, the same evaluation on each member's profile; the block carries member 0's, the kernels' member view the others')
         const size_t nn = (size_t)ctx->n_nodes;
-        ctx->mconsts.assign((size_t)K * GEOAC_MEMC, 0.0);
+        ctx->mconsts.assign((size_t)K * GEOAC_MEMP, 0.0);
         std::vector<double> Tm, rm;
         for(int m = 0; m < K; m++){
-        if(ens){ Tm.assign(ctx->ens_T.begin() + m * nn, ctx->ens_T.begin() + (m + 1) * nn); rm.assign(ctx->ens_rho.begin() + m * nn, ctx->ens_rho.begin() + (m + 1) * nn); }
-        const std::vector<double>& Tv = ens ? Tm : ctx->T;
-        const std::vector<double>& rv = ens ? rm : ctx->rho;
-        const double* slm = ens ? ctx->ens_sl.data() + 4 * nn * m : ctx->sl.data();
+        const bool prof = K > 1;
+        if(prof){ Tm.assign(ctx->ens_T.begin() + m * nn, ctx->ens_T.begin() + (m + 1) * nn); rm.assign(ctx->ens_rho.begin() + m * nn, ctx->ens_rho.begin() + (m + 1) * nn); }
+        const std::vector<double>& Tv = prof ? Tm : ctx->T;
+        const std::vector<double>& rv = prof ? rm : ctx->rho;
+        const double* slm = prof ? ctx->ens_sl.data() + 4 * nn * m : ctx->sl.data();
         double Tg = host_spline_f(ctx->x, Tv, slm, p.z_grnd);
         double rg = host_spline_f(ctx->x, rv, slm + 3 * nn, p.z_grnd);
         double cg = sqrt(kGamR * Tg) * 1000.0;
@@ -803,17 +844,25 @@ static int fan_launch_once(geoac_ctx* ctx){
         P.cbrt_To = cbrt(P.T_o);
         P.P_o = rg * (cg * cg) / kGam * 1000.0;
         P.c000 = sqrt(kGamR * host_spline_f(ctx->x, Tv, slm, 0.0));       // c(0,0,0), 3DStratified.cpp:367
-        double* c = &ctx->mconsts[(size_t)m * GEOAC_MEMC];
+        double* c = &ctx->mconsts[(size_t)m * GEOAC_MEMP];
         c[0] = P.T_o; c[1] = P.P_o; c[2] = P.cbrt_To; c[3] = P.c000;
         }
         P.T_o = ctx->mconsts[0]; P.P_o = ctx->mconsts[1]; P.cbrt_To = ctx->mconsts[2]; P.c000 = ctx->mconsts[3];
         if(ens){
-            HIPCHK(ctx->d_mconsts.ensure(sizeof(double) * ctx->mconsts.size()));
-            HIPCHK(hipMemcpy(ctx->d_mconsts.p, ctx->mconsts.data(), sizeof(double) * ctx->mconsts.size(), hipMemcpyHostToDevice));
+            // member m = s K + k: profile k's state, then source s and the sin / cos of its latitude - the expressions above, per source
+            std::vector<double> mc((size_t)M * GEOAC_MEMC);
+            for(int m = 0; m < M; m++){
+                double* c = &mc[(size_t)m * GEOAC_MEMC];
+                const double* sp = n_src > 1 ? &ctx->sources[3 * (size_t)(m / K)] : p.src;
+                for(int q = 0; q < GEOAC_MEMP; q++) c[q] = ctx->mconsts[(size_t)(m % K) * GEOAC_MEMP + q];
+                c[4] = sp[0]; c[5] = sp[1]; c[6] = sp[2];
+                c[7] = sin(sp[1] * kPi / 180.0); c[8] = cos(sp[1] * kPi / 180.0);
+            }
+            HIPCHK(ctx->d_mconsts.ensure(sizeof(double) * mc.size()));
+            HIPCHK(hipMemcpy(ctx->d_mconsts.p, mc.data(), sizeof(double) * mc.size(), hipMemcpyHostToDevice));
             P.mem_consts = (const double*)ctx->d_mconsts.p;
         }
         }
-        P.src_trig[0] = sin(p.src[1] * kPi / 180.0); P.src_trig[1] = cos(p.src[1] * kPi / 180.0);
     }
     // ---- epoch size: 8192 rows unless a path chunk would pass 40 GiB (three chunks + three contrib buffers <= 160 GiB of the 288).
     //      Measured on the metric fan (GEOAC_S_ROWS sweep, hybrid build): 4096 rows 179 ms per pass, 8192 167, 12288 167, 16384 173 -
@@ -882,7 +931,7 @@ static int fan_launch_once(geoac_ctx* ctx){
             for(int m = 0; m < K; m++){
                 GeoacDevParams Pm = P;
                 Pm.seg = (const double*)ctx->seg.p + (size_t)m * P.nseg * GEOAC_SEGW; Pm.rho = (const double*)ctx->rhot.p + (size_t)m * P.nseg * 4;
-                const double* c = &ctx->mconsts[(size_t)m * GEOAC_MEMC];
+                const double* c = &ctx->mconsts[(size_t)m * GEOAC_MEMP];
                 Pm.T_o = c[0]; Pm.P_o = c[1]; Pm.cbrt_To = c[2]; Pm.c000 = c[3];
                 HIPCHK(geoac_launch_atab_build(&Pm, (double*)ctx->atab.p + GEOAC_ATABW * n_ent * m, tol, ctx->stream));
             }
@@ -1025,7 +1074,7 @@ static int fan_launch_once(geoac_ctx* ctx){
     bool late_pair = false;
     unsigned long long long_bound = (unsigned long long)(plan_stagger_frac * ctx->n_rays);      // live rays of the leading share (an upper bound: what its last launch counted)
     if(compact){
-        for(int b = 0; b < 3; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * ((size_t)P.n_pad + K)));      // (ensembles: + the members' range starts)
+        for(int b = 0; b < 3; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * ((size_t)P.n_pad + M)));      // (ensembles: + the members' range starts)
         HIPCHK(ctx->ncols.ensure(4 * sizeof(int)));
     }
     P.n_cols_bound = P.n_pad;
@@ -1161,7 +1210,7 @@ static int fan_launch_once(geoac_ctx* ctx){
                                         (int*)ctx->colmap[b].p, (int*)ctx->ncols.p + b, block, s));
             Pe.colmap = (const int*)ctx->colmap[b].p; Pe.n_cols = (const int*)ctx->ncols.p + b;
             // (ensembles: each member's columns padded to whole workgroups)
-            Pe.n_cols_bound = (int)std::min<unsigned long long>((unsigned long long)P.n_pad, (live_bound + 63ull) / 64ull * 64ull + (ens ? (unsigned long long)K * block : 0ull));
+            Pe.n_cols_bound = (int)std::min<unsigned long long>((unsigned long long)P.n_pad, (live_bound + 63ull) / 64ull * 64ull + (ens ? (unsigned long long)M * block : 0ull));
             if(Pe.n_cols_bound < 64) Pe.n_cols_bound = 64;
             Pe.slot_lo = 0; Pe.slot_hi = Pe.n_cols_bound;
         }

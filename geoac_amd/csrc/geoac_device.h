@@ -17,6 +17,10 @@
 // are K member tables back to back ([K][nseg][SEGW], [K][nseg][4], [K][nseg+2][ATABW], one lat_trig behind the last), the ray slots are
 // member-major (member m owns [m S, (m+1) S), S = mem_slots, a multiple of 256 with at least one ray-less slot), the records [K][n_rays][legs][32].
 // A kernel instantiated for ensembles finds its member once per workgroup or wave and works on the member view (member_view) of the block.
+//
+// Source sets (geoac_set_sources: the fan's angles from n_src source points in one launch): a member is a (source, profile) pair, m = s K + k
+// with K the profiles of the atmosphere.  Slots, compaction and records are the ensembles' with M = n_src K members ([n_src][K][n_rays][legs][32]);
+// the tables stay per profile (member m reads profile m % K's), and mem_consts carries each member's source beside its profile's reference state.
 #ifndef GEOAC_DEVICE_H_
 #define GEOAC_DEVICE_H_
 
@@ -143,12 +147,15 @@ struct GeoacDevParams {
     long long     smp_cap;
     double*       rec;              // [n_rays][bounces+1][32]
     unsigned long long* counters;   // [0] total steps, [1] active rays after this epoch, [2] error flags, [3] samples emitted
-    // ensembles (n_members > 1); 1 / 0 / NULL for a single profile
-    int           n_members;        // K
+    // ensembles and source sets (n_members > 1); 1 / 0 / NULL / 1 for a single profile and source
+    int           n_members;        // M = n_src K: members of the launch, m = s K + k (source-major)
     int           mem_slots;        // S: ray slots per member
-    const double* mem_consts;       // [K][GEOAC_MEMC]: T_o, P_o, cbrt_To, c000 of each member (host-evaluated as for a single profile)
+    const double* mem_consts;       // [M][GEOAC_MEMC]: T_o, P_o, cbrt_To, c000 of the member's profile (host-evaluated as for a single profile), then src[3] and
+                                    // src_trig[2] of its source (host libm, as for a single source)
+    int           n_profiles;       // K: member tables in seg / rho / atab (member m reads table m % K)
 };
 
-#define GEOAC_MEMC      4       // doubles per member in mem_consts
+#define GEOAC_MEMC      9       // doubles per member in mem_consts
+#define GEOAC_MEMP      4       // ... the first of which belong to the profile
 
 #endif

@@ -310,14 +310,18 @@ DEVINL double rho_eval(const GeoacDevParams& P, int k, double x){
     return __builtin_fma(t, __builtin_fma(t, __builtin_fma(t, q[3], q[2]), q[1]), q[0]);
 }
 
-// ensembles (geoac_device.h): the parameter block as a kernel of a single-profile fan with member m's profile would see it - m's tables and
-// reference state.  m is wave-uniform wherever a kernel derives it (readfirstlane: the pointers stay in scalar registers).
+// ensembles and source sets (geoac_device.h): the parameter block as a kernel of a single fan with member m's profile and source would see
+// it - the tables and reference state of profile m % K, the source m / K.  m is wave-uniform wherever a kernel derives it (readfirstlane: the
+// pointers and the source stay in scalar registers, the member's constants are scalar loads).
 DEVINL void member_view(GeoacDevParams& P, int m){
-    P.seg += (size_t)m * P.nseg * GEOAC_SEGW;
-    P.rho += (size_t)m * P.nseg * 4;
-    if(P.atab) P.atab += (size_t)m * (P.nseg + 2) * GEOAC_ATABW;
+    const int k = m % P.n_profiles;
+    P.seg += (size_t)k * P.nseg * GEOAC_SEGW;
+    P.rho += (size_t)k * P.nseg * 4;
+    if(P.atab) P.atab += (size_t)k * (P.nseg + 2) * GEOAC_ATABW;
     const double* c = P.mem_consts + (size_t)m * GEOAC_MEMC;
     P.T_o = c[0]; P.P_o = c[1]; P.cbrt_To = c[2]; P.c000 = c[3];
+    P.src[0] = c[4]; P.src[1] = c[5]; P.src[2] = c[6];
+    P.src_trig[0] = c[7]; P.src_trig[1] = c[8];
 }
 DEVINL int member_of_slot(const GeoacDevParams& P, int slot){
     const int m = __builtin_amdgcn_readfirstlane(slot) / P.mem_slots;

@@ -162,6 +162,22 @@ int  geoac_set_params(geoac_ctx* ctx, const geoac_params* p);
 /* the parameters as they stand (defaults resolved: vert_limit, xy_limits after an atmosphere upload) and the equation set */
 int  geoac_get_params(geoac_ctx* ctx, geoac_params* p);
 int  geoac_get_eqset(geoac_ctx* ctx, int* eqset);
+
+/* source set: one geoac_fan_launch integrates the fan's angles from n_src source points (a line source, a grid of candidate sources, the
+ * stations of a network), and through every profile when an ensemble of K is loaded.  src: [n_src][3] in the layout of geoac_params.src;
+ * GEOAC_EQ_2D, GEOAC_EQ_3D, GEOAC_EQ_GLOBAL only (a range-dependent set returns GEOAC_E_UNSUPPORTED); n_src >= 1 and n_src * K <=
+ * GEOAC_MAX_MEMBERS, checked here and again at the launch (an ensemble upload may change K in between): GEOAC_E_INVALID.
+ * A member of the launch is a (source, profile) pair, m = s * K + k.  The records of (s, k) are bit-identical to those of a context loaded
+ * with profile k alone whose geoac_params.src is src[s], under every launch-plan option; each source is treated as a single one is (a
+ * height below z_grnd is clamped, the 2-D set reads src[0] only).  While n_src > 1:
+ *   - geoac_fan_fetch, geoac_fan_records_dev and geoac_fan_copy_records_dev cover [n_src][K][n_rays][legs][GEOAC_REC_STRIDE];
+ *   - total_steps is the sum over all members;
+ *   - geoac_set_params keeps the set (its src field is ignored), geoac_get_params reports source 0;
+ *   - sample capture (GEOAC_MODE_WRITE_RAYS / _CAUSTICS), the eigenray searches, geoac_clone and the pool return GEOAC_E_UNSUPPORTED.
+ * n_src == 1 sets geoac_params.src = src[0] and leaves the mode: shapes, launch plan and records are a plain context's again. */
+int  geoac_set_sources(geoac_ctx* ctx, int n_src, const double* src);
+int  geoac_get_sources(geoac_ctx* ctx, int* n_src);
+
 /* c [km/s], u, v [km/s], rho of the uploaded 1-D atmosphere at abscissa x, evaluated on the host (set-up / reporting only) */
 int  geoac_medium_1d(geoac_ctx* ctx, double x, double out[4]);
 
