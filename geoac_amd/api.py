@@ -193,6 +193,7 @@ class FanContext:
         self.n_rays = 0
         self.n_members = 1
         self.n_sources = 1
+        self._n_freq = 1
 
     def _chk(self, rc):
         if rc:
@@ -220,6 +221,7 @@ class FanContext:
         c.n_rays = 0
         c.n_members = 1
         c.n_sources = 1
+        c._n_freq = 1
         if hasattr(self, "_grid_dims"):
             c._grid_dims = self._grid_dims
         return c
@@ -313,6 +315,37 @@ class FanContext:
         self._chk(self.lib.geoac_set_sources(self._h, src.shape[0], _p(src)))
         self.n_sources = src.shape[0]
         self.params.src = (ctypes.c_double * 3)(*src[0])
+
+    def set_frequencies(self, freqs):
+        """frequency set (geoac_set_frequencies): one launch then gives every arrival's attenuation at each of the frequencies [Hz] (at most 16); run() and
+        fetch() are unchanged - the records are those of freq = freqs[0] - and fetch_atten() returns the table [F][n_rays][legs], atten[f] bit-identical
+        to the ATTEN column of a run with set_params(freq=freqs[f]).  One frequency sets Params.freq and leaves the mode."""
+        fr = _arr(freqs)
+        if fr.ndim != 1:
+            raise GeoAcError(f"set_frequencies: freqs must be a one-dimensional array (got shape {fr.shape})")
+        self._chk(self.lib.geoac_set_frequencies(self._h, len(fr), _p(fr)))
+        self._n_freq = len(fr)
+        self.params.freq = float(fr[0])
+
+    @property
+    def n_frequencies(self):
+        """frequencies of the active set (1: none)"""
+        n = ctypes.c_int(0)
+        self._chk(self.lib.geoac_get_frequencies(self._h, ctypes.byref(n)))
+        return n.value
+
+    def fetch_atten(self, out=None):
+        """cumulative attenuation [dB] of the last launch per (frequency, ray, leg): [F][n_rays][legs] (F = 1 without a frequency set: the records' ATTEN
+        column); `out`: a caller-owned C-contiguous float64 array of that shape"""
+        shape = (self._n_freq, self.n_rays, self.params.bounces + 1)
+        if out is None:
+            att = np.empty(shape)
+        else:
+            att = out
+            if not (isinstance(att, np.ndarray) and att.dtype == np.float64 and att.flags.c_contiguous and att.shape == shape):
+                raise GeoAcError(f"fetch_atten(out=): need a C-contiguous float64 array of shape {shape}")
+        self._chk(self.lib.geoac_fan_fetch_atten(self._h, _p(att)))
+        return att
 
     def set_angles(self, theta_deg, phi_deg):
         th, ph = _arr(theta_deg), _arr(phi_deg)

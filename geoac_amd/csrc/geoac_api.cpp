@@ -46,6 +46,9 @@ extern "C" hipError_t geoac_launch_gate(const GeoacDevParams* P, unsigned long l
 extern "C" hipError_t geoac_launch_postpass(const GeoacDevParams* P, int rows, hipStream_t s);
 extern "C" hipError_t geoac_launch_postpass_tab(const GeoacDevParams* P, int rows, hipStream_t s);
 extern "C" hipError_t geoac_launch_atab_build(const GeoacDevParams* P, double* tab, double tol, hipStream_t s);
+extern "C" hipError_t geoac_launch_postpass_freq(const GeoacDevParams* P, const GeoacFreqParams* Q, int rows, hipStream_t s);
+extern "C" hipError_t geoac_launch_accum_freq(const GeoacDevParams* P, const GeoacFreqParams* Q, hipStream_t s);
+extern "C" hipError_t geoac_launch_atten_col0(const double* rec, double* atten, long long n, hipStream_t s);
 
 namespace {
 
@@ -209,6 +212,17 @@ struct geoac_ctx {
     std::vector<double> sources;                  // [n_src][3] while n_src > 1 (prm.src holds source 0)
     int layout_members = 1;                       // n_src K the slot layout was built for
     std::vector<double> ang_th, ang_ph;           // the caller's launch angles (the slot layout is rebuilt when K changes)
+    // frequency sets (geoac_set_frequencies): the attenuation at n_freq frequencies from one launch; prm.freq holds frequency 0, which goes through the
+    // post-pass of a single frequency; none of the buffers below exists, and no kernel of the family runs, while n_freq == 1
+    int n_freq = 1;
+    std::vector<double> freqs;                    // [n_freq] while n_freq > 1
+    std::vector<double> atab_fkey;                // the frequency list the tables were built for (with atab_key)
+    bool atab_ok = true;                          // every frequency's table qualifies (at most a quarter of its entries flagged)
+    DevBuf fcontrib[3];                           // [s_rows][n_freq - 1][n_pad], rotating with path / contrib
+    DevBuf fstate, fatten, ffix, fcnt;            // per-frequency running sums, the [n_freq][n_rays][legs] table, the fix-up list and its counters
+    std::vector<hipEvent_t> evf;                  // per epoch: the frequency post-pass has finished (k_accum_freq may start)
+    int last_n_freq = 1;                          // of the last completed launch
+    unsigned long long freq_fixup_segments = 0;   // last launch: (segment, frequency) pairs the extra frequencies' tables did not serve
     std::string err;
 };
 
@@ -405,7 +419,8 @@ int geoac_destroy(geoac_ctx* ctx){
                        &ctx->nlegend[0], &ctx->nlegend[1], &ctx->nlegend[2],
                        &ctx->ev_row[0], &ctx->ev_row[1], &ctx->ev_row[2], &ctx->ev_m[0], &ctx->ev_m[1], &ctx->ev_m[2],
                        &ctx->ev_amp[0], &ctx->ev_amp[1], &ctx->ev_amp[2], &ctx->nev[0], &ctx->nev[1], &ctx->nev[2], &ctx->smp_out,
-                       &ctx->d_gx, &ctx->d_gy, &ctx->d_gz, &ctx->d_gtab, &ctx->d_gtab8, &ctx->d_consts, &ctx->sub_flags, &ctx->colmap[0], &ctx->colmap[1], &ctx->colmap[2], &ctx->ncols, &ctx->atab, &ctx->ppfix };
+                       &ctx->d_gx, &ctx->d_gy, &ctx->d_gz, &ctx->d_gtab, &ctx->d_gtab8, &ctx->d_consts, &ctx->sub_flags, &ctx->colmap[0], &ctx->colmap[1], &ctx->colmap[2], &ctx->ncols, &ctx->atab, &ctx->ppfix,
+                       &ctx->fcontrib[0], &ctx->fcontrib[1], &ctx->fcontrib[2], &ctx->fstate, &ctx->fatten, &ctx->ffix, &ctx->fcnt };
     for(DevBuf* b : bufs) b->release();
     g_deferred.drain();
     if(ctx->h_counters) hipHostFree(ctx->h_counters);
@@ -414,6 +429,7 @@ int geoac_destroy(geoac_ctx* ctx){
     for(hipEvent_t e : ctx->evs) hipEventDestroy(e);
     for(hipEvent_t e : ctx->evj) hipEventDestroy(e);
     for(hipEvent_t e : ctx->evp) hipEventDestroy(e);
+    for(hipEvent_t e : ctx->evf) hipEventDestroy(e);
     if(ctx->acc_stream) hipStreamDestroy(ctx->acc_stream);
     if(ctx->rk4b_stream) hipStreamDestroy(ctx->rk4b_stream);
     if(ctx->pp_stream) hipStreamDestroy(ctx->pp_stream);
@@ -434,6 +450,7 @@ int geoac_clone(geoac_ctx* src, geoac_ctx** out){
     if(!src->have_atmo) return fail(src, GEOAC_E_INVALID, "clone: no atmosphere uploaded");
     if(src->n_members > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
     if(src->n_src > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a source set is active (geoac_set_sources); set a single source first");
+    if(src->n_freq > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a frequency set is active (geoac_set_frequencies); set a single frequency first");
     geoac_ctx* c = nullptr;
     int rc = geoac_create(&c, src->eqset, src->device);
     if(rc) return rc;
@@ -531,6 +548,7 @@ int geoac_upload_atmo_1d_ensemble(geoac_ctx* ctx, int n_members, int n, const do
 int geoac_refuse_ensemble(geoac_ctx* ctx, const char* what){
     if(!ctx) return GEOAC_OK;
     if(ctx->n_src > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a source set is active (geoac_set_sources); set a single source first");
+    if(ctx->n_freq > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a frequency set is active (geoac_set_frequencies); set a single frequency first");
     if(ctx->n_members <= 1) return GEOAC_OK;
     return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
 }
@@ -559,6 +577,37 @@ int geoac_set_sources(geoac_ctx* ctx, int n_src, const double* src){
 int geoac_get_sources(geoac_ctx* ctx, int* n_src){
     if(!ctx || !n_src) return fail(ctx, GEOAC_E_INVALID, "get_sources: bad arguments");
     *n_src = ctx->n_src;
+    return GEOAC_OK;
+}
+
+int geoac_set_frequencies(geoac_ctx* ctx, int n_freq, const double* freq_hz){
+    if(!ctx) return GEOAC_E_INVALID;
+    if(n_freq < 1 || n_freq > GEOAC_MAX_FREQS || !freq_hz)
+        return fail(ctx, GEOAC_E_INVALID, "set_frequencies: n_freq must be in 1 .. " + std::to_string(GEOAC_MAX_FREQS) + " and freq_hz not NULL");
+    for(int f = 0; f < n_freq; f++)
+        if(!std::isfinite(freq_hz[f]) || !(freq_hz[f] > 0.0)) return fail(ctx, GEOAC_E_INVALID, "set_frequencies: every frequency must be finite and greater than 0");
+    if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "set_frequencies: frequency sets are available for the stratified equation sets only");
+    if(n_freq > 1 && ctx->n_members > 1)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "set_frequencies: not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
+    if(n_freq > 1 && ctx->n_src > 1)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "set_frequencies: not available while a source set is active (geoac_set_sources); set a single source first");
+    ctx->prm.freq = freq_hz[0];
+    ctx->n_freq = n_freq;
+    if(n_freq > 1) ctx->freqs.assign(freq_hz, freq_hz + n_freq);
+    else {                                                        // leaves the mode: nothing of the family is held
+        ctx->freqs.clear();
+        HIPCHK(hipSetDevice(ctx->device));
+        if(ctx->stream) HIPCHK(hipStreamSynchronize(ctx->stream));
+        for(int b = 0; b < 3; b++) ctx->fcontrib[b].release();
+        ctx->fstate.release(); ctx->fatten.release(); ctx->ffix.release(); ctx->fcnt.release();
+    }
+    return GEOAC_OK;
+}
+
+int geoac_get_frequencies(geoac_ctx* ctx, int* n_freq){
+    if(!ctx || !n_freq) return fail(ctx, GEOAC_E_INVALID, "get_frequencies: bad arguments");
+    *n_freq = ctx->n_freq;
     return GEOAC_OK;
 }
 
@@ -659,6 +708,7 @@ int geoac_set_params(geoac_ctx* ctx, const geoac_params* p){
     if(!(p->ds_min > 0) || !(p->ds_max >= p->ds_min)) return fail(ctx, GEOAC_E_INVALID, "ds_min/ds_max");
     ctx->prm = *p;
     if(ctx->n_src > 1){ ctx->prm.src[0] = ctx->sources[0]; ctx->prm.src[1] = ctx->sources[1]; ctx->prm.src[2] = ctx->sources[2]; }      // (a source set stays; source 0 is what geoac_get_params reports)
+    if(ctx->n_freq > 1) ctx->prm.freq = ctx->freqs[0];           // (a frequency set stays; frequency 0 is what geoac_get_params reports)
     if(!(ctx->prm.vert_limit == ctx->prm.vert_limit) && ctx->have_atmo) ctx->prm.vert_limit = ctx->x[ctx->n_nodes - 1];
     if(ctx->have_grid){
         const double ext[4] = { ctx->gx.front(), ctx->gx.back(), ctx->gy.front(), ctx->gy.back() };
@@ -791,6 +841,12 @@ static int fan_launch_once(geoac_ctx* ctx){
         return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available while a source set is active; run the source on a context of its own");
     if(ens && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
         return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available for an ensemble; run the member on a context of its own");
+    const int F = ctx->n_freq;                    // frequencies; the extra ones 1 .. F-1 have a post-pass family of their own
+    if(F > 1 && K > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: a frequency set (geoac_set_frequencies) is not available for an ensemble; upload a single profile or set a single frequency first");
+    if(F > 1 && n_src > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: a frequency set (geoac_set_frequencies) is not available while a source set is active; set a single source or a single frequency first");
+    if(F > 1 && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available while a frequency set is active; set a single frequency first");
+    if(F > 1 && is_grid) return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: frequency sets are available for the stratified equation sets only");
     GeoacDevParams P{};
     P.eqset = ctx->eqset; P.calc_amp = p.calc_amp ? 1 : 0; P.mode = p.mode; P.bounces = p.bounces;
     P.n_rays = ctx->n_rays * M; P.n_pad = ctx->n_pad;
@@ -870,6 +926,7 @@ static int fan_launch_once(geoac_ctx* ctx){
     size_t row_bytes = (size_t)P.pathw * P.n_pad * sizeof(double);
     // (CHUNK_GIB: the cap per path chunk; a device that is shared - several ranks or contexts, torch tensors - can be given a smaller one than the 40 GiB that suit a GPU of its own)
     long long s_rows = (long long)(((unsigned long long)ctx->chunk_gib << 30) / row_bytes);      // round 2: 40 GiB per chunk (config 3: 2760 -> 6900 rows, 21 -> 9 epochs, +8 %); the free-memory clamp below still applies
+    if(F > 1) s_rows = s_rows * (P.pathw + 2) / (P.pathw + 1 + F);      // (the frequency contributions inside the same budget: pathw + 2 doubles per row and column become pathw + 2 + F - 1)
     if(s_rows > 8192) s_rows = 8192;
     if(s_rows < 64) s_rows = 64;
     if(ctx->s_rows_override >= 8) s_rows = ctx->s_rows_override;
@@ -878,8 +935,8 @@ static int fan_launch_once(geoac_ctx* ctx){
         size_t free_b = 0, total_b = 0;
         if(hipMemGetInfo(&free_b, &total_b) == hipSuccess){
             size_t held = 0;
-            for(int b = 0; b < 3; b++) held += ctx->path[b].bytes + ctx->contrib[b].bytes;
-            const size_t per_row = (size_t)(ctx->two_chunks ? 2 : 3) * (row_bytes + 2 * (size_t)P.n_pad * sizeof(double));
+            for(int b = 0; b < 3; b++) held += ctx->path[b].bytes + ctx->contrib[b].bytes + ctx->fcontrib[b].bytes;
+            const size_t per_row = (size_t)(ctx->two_chunks ? 2 : 3) * (row_bytes + (2 + (size_t)(F - 1)) * (size_t)P.n_pad * sizeof(double));
             const double budget = 0.8 * (double)(free_b + held);
             if((double)per_row * (double)s_rows > budget){
                 long long fit = (long long)(budget / (double)per_row);
@@ -924,8 +981,10 @@ static int fan_launch_once(geoac_ctx* ctx){
         const double key[7] = { P.freq, P.tweak_abs, P.T_o, P.P_o, P.r_earth, D, tol };
         P.atab_D = D; P.atab_lo = P.x_min - D;
         const size_t n_ent = (size_t)P.nseg + 2;
-        if(ctx->atab_version != ctx->atmo_version || memcmp(key, ctx->atab_key, sizeof(key)) != 0 || ctx->atab_mkey != ctx->mconsts){
-            HIPCHK(ctx->atab.ensure(sizeof(double) * (GEOAC_ATABW * n_ent * K + 2 * (size_t)GEOAC_LAT_N)));      // (+ the latitude table behind the last one)
+        // frequency sets: F tables back to back (K = 1 there), table f built for freqs[f] by the same kernel - table 0 is the table of a single frequency
+        const size_t n_tab = (size_t)K * F;
+        if(ctx->atab_version != ctx->atmo_version || memcmp(key, ctx->atab_key, sizeof(key)) != 0 || ctx->atab_mkey != ctx->mconsts || ctx->atab_fkey != ctx->freqs){
+            HIPCHK(ctx->atab.ensure(sizeof(double) * (GEOAC_ATABW * n_ent * n_tab + 2 * (size_t)GEOAC_LAT_N)));      // (+ the latitude table behind the last one)
             // ensembles: one launch per member on the host-side member view, in member order - each launch also writes the latitude table behind
             // its own table, where the next member's table then goes: the last launch leaves it behind the last table
             for(int m = 0; m < K; m++){
@@ -935,22 +994,35 @@ static int fan_launch_once(geoac_ctx* ctx){
                 Pm.T_o = c[0]; Pm.P_o = c[1]; Pm.cbrt_To = c[2]; Pm.c000 = c[3];
                 HIPCHK(geoac_launch_atab_build(&Pm, (double*)ctx->atab.p + GEOAC_ATABW * n_ent * m, tol, ctx->stream));
             }
-            std::vector<double> h(GEOAC_ATABW * n_ent * K);
+            for(int f = 1; f < F; f++){
+                GeoacDevParams Pf = P;
+                Pf.freq = ctx->freqs[(size_t)f];
+                HIPCHK(geoac_launch_atab_build(&Pf, (double*)ctx->atab.p + GEOAC_ATABW * n_ent * f, tol, ctx->stream));
+            }
+            std::vector<double> h(GEOAC_ATABW * n_ent * n_tab);
             HIPCHK(hipMemcpyAsync(h.data(), ctx->atab.p, sizeof(double) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            ctx->atab_entries = (int)(n_ent * K); ctx->atab_flagged = 0; ctx->atab_worst = 0.0;
-            for(size_t e = 0; e < n_ent * K; e++){
+            ctx->atab_entries = (int)(n_ent * n_tab); ctx->atab_flagged = 0; ctx->atab_worst = 0.0;
+            for(size_t e = 0; e < n_ent * n_tab; e++){
                 if(h[e * GEOAC_ATABW] < 0.0) ctx->atab_flagged++;
                 else ctx->atab_worst = std::max(ctx->atab_worst, h[e * GEOAC_ATABW + GEOAC_ATABW - 1]);
             }
+            // frequency sets: every frequency's table has to qualify on its own (below)
+            ctx->atab_ok = true;
+            for(int f = 0; f < F && F > 1; f++){
+                size_t fl = 0;
+                for(size_t e = 0; e < n_ent; e++) if(h[((size_t)f * n_ent + e) * GEOAC_ATABW] < 0.0) fl++;
+                if(4 * fl > n_ent) ctx->atab_ok = false;
+            }
             memcpy(ctx->atab_key, key, sizeof(key));
             ctx->atab_mkey = ctx->mconsts;
+            ctx->atab_fkey = ctx->freqs;
             ctx->atab_version = ctx->atmo_version;
         }
         // a profile most of whose segments the interpolant cannot serve (very long segments) keeps the exact post-pass
-        if(4 * ctx->atab_flagged <= ctx->atab_entries){
+        if(F > 1 ? ctx->atab_ok : (4 * ctx->atab_flagged <= ctx->atab_entries)){
             P.atab = (const double*)ctx->atab.p; P.atab_on = 1;
-            P.lat_trig = P.atab + (size_t)GEOAC_ATABW * n_ent * K;
+            P.lat_trig = P.atab + (size_t)GEOAC_ATABW * n_ent * n_tab;
             P.ppfix_cap = ctx->ppfix_cap;
             HIPCHK(ctx->ppfix.ensure(sizeof(int) * 2 * (size_t)P.ppfix_cap));
             P.ppfix = (int*)ctx->ppfix.p;
@@ -1099,10 +1171,11 @@ static int fan_launch_once(geoac_ctx* ctx){
         for(int b = 0; b < n_chunks && e == hipSuccess; b++){
             e = ctx->path[b].ensure(row_bytes * (size_t)P.s_rows);
             if(e == hipSuccess) e = ctx->contrib[b].ensure(sizeof(double) * 2 * (size_t)P.n_pad * P.s_rows);
+            if(e == hipSuccess && F > 1) e = ctx->fcontrib[b].ensure(sizeof(double) * (size_t)(F - 1) * (size_t)P.n_pad * P.s_rows);
         }
         if(e == hipSuccess) break;
         (void)hipGetLastError();
-        for(int b = 0; b < 3; b++){ ctx->path[b].release(); ctx->contrib[b].release(); }
+        for(int b = 0; b < 3; b++){ ctx->path[b].release(); ctx->contrib[b].release(); ctx->fcontrib[b].release(); }
         if(e != hipErrorOutOfMemory || P.s_rows < 32 || ctx->s_rows_override >= 8) return hipfail(ctx, e, "path chunks");
         P.s_rows /= 2;
     }
@@ -1140,6 +1213,26 @@ static int fan_launch_once(geoac_ctx* ctx){
         HIPCHK(hipEventRecord(ctx->ev_cu, ctx->stream));
         HIPCHK(hipStreamWaitEvent(s, ctx->ev_cu, 0));
     }
+    // frequency sets: the block of the extra frequencies' kernels; their running sums, the attenuation table and the list counters start from zero
+    GeoacFreqParams Q{};
+    if(F > 1){
+        Q.n_extra = F - 1;
+        for(int f = 1; f < F; f++) Q.freq[f - 1] = ctx->freqs[(size_t)f];
+        Q.atab = P.atab_on ? P.atab + (size_t)GEOAC_ATABW * ((size_t)P.nseg + 2) : nullptr;
+        const size_t n_att = (size_t)F * P.n_rays * ctx->legs;
+        HIPCHK(ctx->fstate.ensure(sizeof(double) * 3 * (size_t)(F - 1) * P.n_pad));
+        HIPCHK(ctx->fatten.ensure(sizeof(double) * n_att));
+        HIPCHK(ctx->fcnt.ensure(2 * sizeof(unsigned long long)));
+        Q.state = (double*)ctx->fstate.p; Q.atten = (double*)ctx->fatten.p; Q.cnt = (unsigned long long*)ctx->fcnt.p;
+        if(P.atab_on){
+            Q.fix_cap = (int)std::min<long long>((long long)P.ppfix_cap * (F - 1), 4ll << 20);
+            HIPCHK(ctx->ffix.ensure(sizeof(int) * 3 * (size_t)Q.fix_cap));
+            Q.fix = (int*)ctx->ffix.p;
+        }
+        HIPCHK(hipMemsetAsync(ctx->fstate.p, 0, sizeof(double) * 3 * (size_t)(F - 1) * P.n_pad, s));
+        HIPCHK(hipMemsetAsync(ctx->fatten.p, 0, sizeof(double) * n_att, s));
+        HIPCHK(hipMemsetAsync(ctx->fcnt.p, 0, 2 * sizeof(unsigned long long), s));
+    }
     HIPCHK(hipMemsetAsync(ctx->counters.p, 0, 32 * sizeof(unsigned long long), s));
     HIPCHK(hipEventRecord(ctx->ev0, s));
     HIPCHK(geoac_launch_init(&P, s));
@@ -1152,6 +1245,8 @@ static int fan_launch_once(geoac_ctx* ctx){
     unsigned long long live = 1, live_bound = (unsigned long long)P.n_pad;
     // post-pass of one epoch on the second stream; gate_expected > 0: only after that many RK4 workgroups of this fan are resident
     auto enqueue_post = [&](GeoacDevParams Pq, size_t e, unsigned long long gate_expected) -> int {
+        GeoacFreqParams Qq = Q;
+        if(F > 1) Qq.contrib = (double*)ctx->fcontrib[e % (size_t)n_chunks].p;
         HIPCHK(hipStreamWaitEvent(sp, ctx->evs[4 * e + 1], 0));
         if(gate_expected > 0 && sp != s && !ctx->no_gate && !cu_split) HIPCHK(geoac_launch_gate(&Pq, gate_expected, sp));
         HIPCHK(hipEventRecord(ctx->evs[4 * e + 2], sp));
@@ -1178,7 +1273,21 @@ static int fan_launch_once(geoac_ctx* ctx){
             HIPCHK(hipEventRecord(ctx->evp[e], sp));
             HIPCHK(hipStreamWaitEvent(sa, ctx->evp[e], 0));
         }
+        if(F > 1){
+            // the extra frequencies behind the post-pass of frequency 0 on its stream, their sums behind k_accum on its own: the chunk is free again
+            // (evs[4e + 3]) once both have finished
+            if(Qq.atab) HIPCHK(hipMemsetAsync(ctx->fcnt.p, 0, sizeof(unsigned long long), sp));      // the list of this launch is empty
+            HIPCHK(geoac_launch_postpass_freq(&Pq, &Qq, Pq.s_rows, sp));
+            if(sa != sp){
+                while(ctx->evf.size() < e + 1){ hipEvent_t ev; HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); ctx->evf.push_back(ev); }
+                HIPCHK(hipEventRecord(ctx->evf[e], sp));
+            }
+        }
         HIPCHK(geoac_launch_accum(&Pq, sa));
+        if(F > 1){
+            if(sa != sp) HIPCHK(hipStreamWaitEvent(sa, ctx->evf[e], 0));
+            HIPCHK(geoac_launch_accum_freq(&Pq, &Qq, sa));
+        }
         HIPCHK(hipEventRecord(ctx->evs[4 * e + 3], sa));
         return GEOAC_OK;
     };
@@ -1284,13 +1393,17 @@ static int fan_launch_once(geoac_ctx* ctx){
     }
     HIPCHK(geoac_launch_arrival(&P, s));           // inclination, back azimuth, range, amplitude of every arrival (k_arrival), beside the last post-pass
     HIPCHK(hipStreamWaitEvent(s, ctx->evs[4 * (ctx->n_epochs - 1) + 3], 0));
+    if(F > 1) HIPCHK(geoac_launch_atten_col0((const double*)ctx->rec.p, (double*)ctx->fatten.p, (long long)P.n_rays * ctx->legs, s));      // row 0: the records' column
     HIPCHK(hipEventRecord(ctx->ev1, s));
     HIPCHK(hipMemcpyAsync(ctx->h_counters + 8, ctx->counters.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     ctx->n_samples = ctx->h_counters[8 + 3];
     {   unsigned long long fx = 0;
         HIPCHK(hipMemcpy(&fx, (const unsigned long long*)ctx->counters.p + GEOAC_CNT_PPFLAG + 1, sizeof(fx), hipMemcpyDeviceToHost));
-        ctx->pp_fixup_segments = fx; }
+        ctx->pp_fixup_segments = fx;
+        ctx->freq_fixup_segments = 0;
+        if(F > 1) HIPCHK(hipMemcpy(&ctx->freq_fixup_segments, (const unsigned long long*)ctx->fcnt.p + 1, sizeof(fx), hipMemcpyDeviceToHost)); }
+    ctx->last_n_freq = F;
     if(ctx->trace_epochs && P.trio){
         unsigned long long v = 0;
         HIPCHK(hipMemcpy(&v, (const unsigned long long*)ctx->counters.p + 30, sizeof(v), hipMemcpyDeviceToHost));
@@ -1367,7 +1480,7 @@ int geoac_abs_table_info(geoac_ctx* ctx, int* entries, int* flagged, uint64_t* f
     if(worst_rel_err) *worst_rel_err = ctx->lastP.atab_on ? ctx->atab_worst : 0.0;
     if(entries) *entries = ctx->lastP.atab_on ? ctx->atab_entries : 0;
     if(flagged) *flagged = ctx->lastP.atab_on ? ctx->atab_flagged : 0;
-    if(fixup_segments) *fixup_segments = (uint64_t)ctx->pp_fixup_segments;
+    if(fixup_segments) *fixup_segments = (uint64_t)(ctx->pp_fixup_segments + ctx->freq_fixup_segments);
     return GEOAC_OK;
 }
 
@@ -1408,6 +1521,39 @@ int geoac_fan_fetch(geoac_ctx* ctx, double* rec_host, uint64_t* total_steps){
         HIPCHK(hipStreamSynchronize(ctx->stream));
     }
     if(total_steps) *total_steps = ctx->total_steps;
+    return GEOAC_OK;
+}
+
+int geoac_fan_atten_dev(geoac_ctx* ctx, void** dev_ptr, size_t* bytes){
+    if(!ctx || !ctx->ran) return fail(ctx, GEOAC_E_INVALID, "fan_atten_dev: no completed launch");
+    if(ctx->lastP.n_members > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_atten_dev: not available for an ensemble or a source set");
+    if(ctx->n_freq != ctx->last_n_freq) return fail(ctx, GEOAC_E_INVALID, "fan_atten_dev: the frequency set has changed since the last completed launch");
+    const size_t n = (size_t)ctx->n_rays * ctx->legs;
+    if(ctx->last_n_freq == 1){
+        // a single frequency: the table is the records' column, gathered on request (no launch of a plain context pays for it)
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(ctx->fatten.ensure(sizeof(double) * n));
+        HIPCHK(geoac_launch_atten_col0((const double*)ctx->rec.p, (double*)ctx->fatten.p, (long long)n, ctx->stream));
+    }
+    if(dev_ptr) *dev_ptr = ctx->fatten.p;
+    if(bytes) *bytes = sizeof(double) * n * (size_t)ctx->last_n_freq;
+    return GEOAC_OK;
+}
+
+int geoac_fan_fetch_atten(geoac_ctx* ctx, double* atten_host){
+    if(!ctx || !ctx->ran || !atten_host) return fail(ctx, GEOAC_E_INVALID, "fan_fetch_atten: no completed launch / null buffer");
+    if(ctx->lastP.n_members > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_fetch_atten: not available for an ensemble or a source set");
+    if(ctx->n_freq != ctx->last_n_freq) return fail(ctx, GEOAC_E_INVALID, "fan_fetch_atten: the frequency set has changed since the last completed launch");
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->n_rays * ctx->legs;
+    if(ctx->last_n_freq == 1){
+        // a single frequency: the records' GEOAC_REC_ATTEN column, as a strided copy
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipMemcpy2D(atten_host, sizeof(double), (const double*)ctx->rec.p + GEOAC_REC_ATTEN, sizeof(double) * GEOAC_REC_STRIDE, sizeof(double), n, hipMemcpyDeviceToHost));
+        return GEOAC_OK;
+    }
+    HIPCHK(hipMemcpyAsync(atten_host, ctx->fatten.p, sizeof(double) * n * (size_t)ctx->last_n_freq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
     return GEOAC_OK;
 }
 

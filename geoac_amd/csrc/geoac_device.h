@@ -21,6 +21,14 @@
 // Source sets (geoac_set_sources: the fan's angles from n_src source points in one launch): a member is a (source, profile) pair, m = s K + k
 // with K the profiles of the atmosphere.  Slots, compaction and records are the ensembles' with M = n_src K members ([n_src][K][n_rays][legs][32]);
 // the tables stay per profile (member m reads profile m % K's), and mem_consts carries each member's source beside its profile's reference state.
+//
+// Frequency sets (geoac_set_frequencies: the attenuation at F frequencies from one launch): the absorption tables are F tables back to back
+// ([F][nseg+2][ATABW], the lat_trig behind the last; with a member dimension it would go in front: table (k F + f)).  Frequency 0 is geoac_params.freq and
+// goes through the kernels of a single frequency, untouched; the frequencies 1 .. F-1 have a post-pass family of their own (k_postpass_freq, k_ppfix_freq,
+// k_postpass_freq_exact, k_accum_freq) that takes GeoacFreqParams beside the parameter block:
+//   fcontrib    [S_rows][F-1][n_pad]    per-segment attenuation increments of the extra frequencies, rotating with the path chunks
+//   fstate      [F-1][3][n_pad]         running attenuation, per-leg partial sum and current leg of the per-frequency sums (as ST_AT, ST_LAT, ST_PLEG)
+//   atten       [F][n_rays][legs]       cumulative attenuation per (frequency, ray, leg), caller's ray order; row 0 is a copy of the records' column
 #ifndef GEOAC_DEVICE_H_
 #define GEOAC_DEVICE_H_
 
@@ -153,6 +161,20 @@ struct GeoacDevParams {
     const double* mem_consts;       // [M][GEOAC_MEMC]: T_o, P_o, cbrt_To, c000 of the member's profile (host-evaluated as for a single profile), then src[3] and
                                     // src_trig[2] of its source (host libm, as for a single source)
     int           n_profiles;       // K: member tables in seg / rho / atab (member m reads table m % K)
+};
+
+#define GEOAC_MAXF      16      // frequencies of a set (GEOAC_MAX_FREQS)
+// what the kernels of the extra frequencies 1 .. F-1 of a frequency set take beside GeoacDevParams (which stays the block of a single frequency)
+struct GeoacFreqParams {
+    int           n_extra;          // F - 1
+    int           fix_cap;          // entries of the fix-up list
+    double        freq[GEOAC_MAXF - 1];   // frequencies 1 .. F-1 [Hz]
+    const double* atab;             // [F-1][nseg + 2][GEOAC_ATABW]: the tables of the frequencies 1 .. F-1 (NULL on the exact path)
+    double*       contrib;          // [s_rows][F-1][n_pad] of the current chunk
+    double*       state;            // [F-1][3][n_pad]: running attenuation, per-leg partial sum, current leg
+    double*       atten;            // [F][n_rays][legs]
+    int*          fix;              // fix-up list of k_postpass_freq: (column, chunk row, frequency) of the segments a table did not serve
+    unsigned long long* cnt;        // [0] entries of the list of the current launch, [1] segments of the fan the tables did not serve
 };
 
 #define GEOAC_MEMC      9       // doubles per member in mem_consts

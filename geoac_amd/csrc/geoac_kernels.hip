@@ -2490,6 +2490,153 @@ __global__ void __launch_bounds__(256) k_ppfix(GeoacDevParams P){
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Frequency sets (geoac_set_frequencies): the attenuation increments of the frequencies 1 .. F-1, behind the post-pass of frequency 0 on its stream.
+// Everything about a path segment but the table entry is the same for every frequency, so it is formed once.
+// ------------------------------------------------------------------------------------------------
+// k_postpass_freq: one thread walks GEOAC_PP_ROWS consecutive segments of one ray, as k_postpass_tab does, in two phases.  First the rows: each path row is
+// read once, and the segment's geometry (pp_geom), clamped abscissa, spline segment and atab_locate give (entry, offset t, ds_at), kept in LDS ([row][thread]:
+// 20 B x 16 rows x 128 threads = 40 KiB per workgroup - which also keeps these workgroups off the CUs that hold an RK4 workgroup with its table, as pp_lds_pad
+// does for k_postpass_tab).  Then, per frequency, the rows again with that frequency's table entry in registers: atab_eval(entry, t) * ds_at - the operations of
+// k_postpass_tab on the same operands, hence the same bits - and an entry is fetched only where the midpoint changes spline segment, not per row and
+// frequency.  The travel time is not formed again.  Segments a frequency's table does not serve go to the list of k_ppfix_freq.
+#define GEOAC_PF_THREADS 128
+DEVINL double freq_of(const GeoacFreqParams& Q, int f){ return Q.freq[f]; }
+template <class EQ>
+__global__ void __launch_bounds__(GEOAC_PF_THREADS) k_postpass_freq(GeoacDevParams P, GeoacFreqParams Q, int rows, int gy0){
+    constexpr int PW = EQ::PW, R = GEOAC_PP_ROWS, NT = GEOAC_PF_THREADS;
+    extern __shared__ double pf_lds[];
+    double* const lt = pf_lds + threadIdx.x;                      // offset within the entry
+    double* const ld = pf_lds + R * NT + threadIdx.x;             // ds_at
+    int* const le = (int*)(pf_lds + 2 * R * NT) + threadIdx.x;    // entry (~entry: beyond the strips)
+    const size_t np = (size_t)P.n_pad;
+    const int ncol = P.colmap ? *P.n_cols : P.n_pad;
+    const int col = (int)blockIdx.x * NT + (int)threadIdx.x;
+    if(col >= ncol) return;
+    const int nr = P.nrows[col];
+    const int slot = P.colmap ? P.colmap[col] : col;
+    double aux[2] = { 0.0, 0.0 };
+    EQ::pp_aux(P, P.state + slot, np, aux);
+    const int i0 = (gy0 + (int)blockIdx.y) * R;
+    if(i0 + 1 >= nr) return;
+    const int i1 = min(i0 + R, nr - 1);                           // segments i0 .. i1 - 1
+    {
+        const double* a = P.path + ((size_t)i0 * PW) * np + col;
+        double A[PW], B[PW];
+        #pragma unroll
+        for(int c = 0; c < PW; c++) A[c] = a[(size_t)c * np];
+        double ref[3] = { 0.15915494309189532, 0.0, 1.0 };
+        double x0 = 1.0, x1 = 0.0;                                // bounds of the spline segment in hand (k)
+        int k = -1;
+        for(int i = i0; i < i1; i++){
+            const double* b = P.path + ((size_t)(i + 1) * PW) * np + col;
+            #pragma unroll
+            for(int c = 0; c < PW; c++) B[c] = b[(size_t)c * np];
+            PPGeom G;
+            EQ::pp_geom(P, aux, A, B, G, ref);
+            const double xe = clampq(G.x, P.x_min, P.x_max);
+            if(!((xe >= x0) & (xe <= x1))){                       // (also the first segment)
+                k = seg_find(P.seg, P.nseg, xe, k < 0 ? (int)((xe - P.x_min) * P.seg_per_x) : k);
+                const double* p = P.seg + (size_t)k * GEOAC_SEGW;
+                x0 = p[0]; x1 = p[1];
+            }
+            double t; bool out;
+            const int e = atab_locate(P, G.x, xe, k, x0, t, out);
+            const int j = i - i0;
+            lt[j * NT] = t; ld[j * NT] = G.ds_at; le[j * NT] = out ? ~e : e;
+            #pragma unroll
+            for(int c = 0; c < PW; c++) A[c] = B[c];
+        }
+    }
+    const size_t n_ent = (size_t)P.nseg + 2;
+    for(int f = 0; f < Q.n_extra; f++){
+        double tb[19];
+        #pragma unroll
+        for(int c = 0; c < 19; c++) tb[c] = 0.0;
+        int ent = -1;
+        for(int i = i0; i < i1; i++){
+            const int j = i - i0;
+            const int ee = le[j * NT];
+            const bool out = ee < 0;
+            const int e = out ? ~ee : ee;
+            if(e != ent){
+                const double* q = Q.atab + ((size_t)f * n_ent + (size_t)e) * GEOAC_ATABW;
+                #pragma unroll
+                for(int c = 0; c < 19; c++) tb[c] = q[c];
+                ent = e;
+            }
+            const double at = atab_eval(tb, lt[j * NT]) * ld[j * NT];
+            if(out | (tb[0] < 0.0)){                              // not served by this frequency's table (rare): listed for k_ppfix_freq
+                atomicAdd(&Q.cnt[1], 1ull);
+                const unsigned long long q = atomicAdd(&Q.cnt[0], 1ull);
+                if(q < (unsigned long long)Q.fix_cap){ Q.fix[3 * q] = col; Q.fix[3 * q + 1] = i; Q.fix[3 * q + 2] = f; }
+                else atomicOr(&P.counters[2], 16ull);             // (list full: the host repeats the fan with the exact post-pass)
+            }
+            Q.contrib[((size_t)i * Q.n_extra + f) * np + col] = at;
+        }
+    }
+}
+
+// k_ppfix_freq: the (segment, frequency) pairs k_postpass_freq listed, exactly - k_ppfix with the pair's frequency
+template <class EQ>
+__global__ void __launch_bounds__(256) k_ppfix_freq(GeoacDevParams P, GeoacFreqParams Q){
+    constexpr int PW = EQ::PW;
+    const size_t np = (size_t)P.n_pad;
+    unsigned long long n = Q.cnt[0];
+    if(n > (unsigned long long)Q.fix_cap) n = (unsigned long long)Q.fix_cap;
+    for(unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (unsigned long long)gridDim.x * blockDim.x){
+        const int col = Q.fix[3 * q], i = Q.fix[3 * q + 1], f = Q.fix[3 * q + 2];
+        const int slot = P.colmap ? P.colmap[col] : col;
+        double aux[2] = { 0.0, 0.0 };
+        EQ::pp_aux(P, P.state + slot, np, aux);
+        const double* a = P.path + ((size_t)i * PW) * np + col;
+        double A[PW], B[PW];
+        #pragma unroll
+        for(int c = 0; c < PW; c++){ A[c] = a[(size_t)c * np]; B[c] = a[(size_t)(PW + c) * np]; }
+        double ref[3] = { 0.15915494309189532, 0.0, 1.0 };
+        PPGeom G;
+        EQ::pp_geom(P, aux, A, B, G, ref);
+        const double xe = clampq(G.x, P.x_min, P.x_max);
+        const int k = seg_find(P.seg, P.nseg, xe, (int)((xe - P.x_min) * P.seg_per_x));
+        double T, u, v; seg_eval_f(P.seg + (size_t)k * GEOAC_SEGW, xe, T, u, v);
+        const double qT = kGamR * T;
+        Q.contrib[((size_t)i * Q.n_extra + f) * np + col] = suthbass_alpha(P, G.x - P.r_earth, qT * frsq(qT), rho_eval(P, k, xe), freq_of(Q, f), P.T_o, P.P_o, P.cbrt_To) * G.ds_at;
+    }
+}
+
+// k_postpass_freq_exact (ABS_TABLE=0, the fallback, a table that does not qualify): one thread per path segment as k_postpass; geometry and medium at the
+// midpoint once, as pp_exact forms them, then SuthBass_Alpha once per frequency with the arguments EQ::segment passes
+template <class EQ>
+__global__ void __launch_bounds__(256) k_postpass_freq_exact(GeoacDevParams P, GeoacFreqParams Q, int rows){
+    constexpr int PW = EQ::PW;
+    const size_t np = (size_t)P.n_pad;
+    const int bx = (P.n_cols_bound + 255) / 256;
+    const long long total = (long long)bx * (rows - 1);
+    const int ncol = P.colmap ? *P.n_cols : P.n_pad;
+    for(long long w = blockIdx.x; w < total; w += gridDim.x){
+        const int i = (int)(w / bx);
+        const int col = (int)(w % bx) * 256 + (int)threadIdx.x;
+        if(col >= ncol) continue;
+        if(i + 1 >= P.nrows[col]) continue;
+        const int slot = P.colmap ? P.colmap[col] : col;
+        double aux[2] = { 0.0, 0.0 };
+        EQ::pp_aux(P, P.state + slot, np, aux);
+        const double* a = P.path + ((size_t)i * PW) * np + col;
+        double A[PW], B[PW];
+        #pragma unroll
+        for(int c = 0; c < PW; c++){ A[c] = a[(size_t)c * np]; B[c] = a[(size_t)(PW + c) * np]; }
+        PPGeom G;
+        EQ::pp_geom(P, aux, A, B, G);
+        const double xe = clampd(G.x, P.x_min, P.x_max);
+        const int k = seg_guess(P.seg, P, xe);
+        double T, u, v; seg_eval_f(P.seg + (size_t)k * GEOAC_SEGW, xe, T, u, v);
+        const double qT = kGamR * T;
+        const double c_snd = qT * frsq(qT), rho = rho_eval(P, k, xe), zr = G.x - P.r_earth;
+        for(int f = 0; f < Q.n_extra; f++)
+            Q.contrib[((size_t)i * Q.n_extra + f) * np + col] = suthbass_alpha(P, zr, c_snd, rho, freq_of(Q, f), P.T_o, P.P_o, P.cbrt_To) * G.ds_at;
+    }
+}
+
 // k_atab_build: one thread per table entry (see atab_eval).  Entry e < nseg: spline segment e; nseg: the strip [x_min - D, x_min];
 // nseg + 1: [x_max, x_max + D].  The exact value at abscissa x is what the exact post-pass computes there: medium at the clamped abscissa,
 // height x - r_earth unclamped.
@@ -2702,6 +2849,75 @@ __global__ void __launch_bounds__(256) k_accum(GeoacDevParams P){
     }
     st[ST_TT * np] = tt; st[ST_AT * np] = at; st[ST_PLEG * np] = (double)leg;
     st[ST_LTT * np] = ltt; st[ST_LAT * np] = lat;
+}
+
+// k_accum_freq: the sums of k_accum for the attenuation of one extra frequency of a frequency set (grid y): one thread per (ray, frequency), the same leg-end
+// bookkeeping (legend, nlegend, cur_end), both summation forms and the eight-row variant - one add per row, in row order, the per-leg partial sum folded in at
+// the leg end: the order bit identity with a single run rests on.  The running sums carry from epoch to epoch in Q.state as ST_AT, ST_LAT, ST_PLEG do in the state.
+__global__ void __launch_bounds__(256) k_accum_freq(GeoacDevParams P, GeoacFreqParams Q){
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if(col >= (P.colmap ? *P.n_cols : P.n_pad)) return;
+    const size_t np = (size_t)P.n_pad;
+    const int nr = P.nrows[col];
+    if(nr < 2) return;
+    const int f = (int)blockIdx.y, nx = Q.n_extra;
+    const int slot = P.colmap ? P.colmap[col] : col;
+    double* st = Q.state + (size_t)f * 3 * np + slot;
+    double at = st[0], lat = st[np];
+    int leg = (int)st[2 * np];
+    const int ne = P.nlegend[col];
+    int e = 0;
+    int next_end = (e < ne) ? P.legend[(size_t)e * np + col] : 0x7fffffff;
+    int cur_end = -1;
+    const bool rays_form = P.rays_form != 0;
+    const int legs = P.bounces + 1;
+    double* const out = Q.atten + ((size_t)(f + 1) * P.n_rays + (size_t)(P.perm ? P.perm[slot] : slot)) * legs;
+    const double* const cb = Q.contrib + (size_t)f * np + col;
+    const size_t rs = (size_t)nx * np;                            // row stride
+    int i_begin = 0;
+    if(P.accum_batch && !rays_form){
+        for(int i0 = 0; i0 + 1 < nr; i0 += 8){
+            double c1[8];
+            #pragma unroll
+            for(int j = 0; j < 8; j++){
+                const int i = i0 + j;
+                c1[j] = cb[(size_t)(i + 1 < nr ? i : 0) * rs];
+            }
+            #pragma unroll
+            for(int j = 0; j < 8; j++){
+                const int i = i0 + j;
+                if(i + 1 >= nr || i == cur_end) continue;
+                lat += c1[j];
+                if(i + 1 == next_end){
+                    at += lat; lat = 0.0;
+                    out[leg] = at;
+                    leg++; cur_end = i + 1; e++;
+                    next_end = (e < ne) ? P.legend[(size_t)e * np + col] : 0x7fffffff;
+                }
+            }
+        }
+        i_begin = nr;
+    }
+    for(int i = i_begin; i + 1 < nr; i++){
+        if(i == cur_end) continue;
+        const double c = cb[(size_t)i * rs];
+        const bool last = (i + 1 == next_end);
+        if(rays_form){ if(!last) at += c; }
+        else lat += c;
+        if(last){
+            if(!rays_form){ at += lat; lat = 0.0; }
+            out[leg] = at;
+            leg++; cur_end = i + 1; e++;
+            next_end = (e < ne) ? P.legend[(size_t)e * np + col] : 0x7fffffff;
+        }
+    }
+    st[0] = at; st[np] = lat; st[2 * np] = (double)leg;
+}
+
+// row 0 of the attenuation table of a frequency set: the records' GEOAC_REC_ATTEN column (frequency 0 goes through k_accum)
+__global__ void __launch_bounds__(256) k_atten_col0(const double* __restrict__ rec, double* __restrict__ atten, long long n){
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if(i < n) atten[i] = rec[i * GEOAC_REC_STRIDE + GEOAC_REC_ATTEN];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3232,3 +3448,53 @@ extern "C" hipError_t geoac_launch_accum(const GeoacDevParams* P, hipStream_t s)
     return hipGetLastError();
 }
 #endif  // GEOAC_NO_LAUNCHERS
+
+// ---- frequency sets: the post-pass family of the frequencies 1 .. F-1 ----
+#define GEOAC_DISPATCH_EQ_STRAT(P, CALL) \
+    switch((P)->eqset * 2 + ((P)->calc_amp ? 1 : 0)){ \
+        case GEOAC_EQ_GLOBAL * 2 + 1: { using EQ = EqGlobal<true>;  CALL; } break; \
+        case GEOAC_EQ_GLOBAL * 2 + 0: { using EQ = EqGlobal<false>; CALL; } break; \
+        case GEOAC_EQ_3D * 2 + 1:     { using EQ = Eq3D<true>;      CALL; } break; \
+        case GEOAC_EQ_3D * 2 + 0:     { using EQ = Eq3D<false>;     CALL; } break; \
+        case GEOAC_EQ_2D * 2 + 1:     { using EQ = Eq2D<true>;      CALL; } break; \
+        case GEOAC_EQ_2D * 2 + 0:     { using EQ = Eq2D<false>;     CALL; } break; \
+        default: return hipErrorNotSupported; }
+
+// attenuation increments of the extra frequencies for one epoch: through their tables + the fix-up of the listed pairs (the list's counter was zeroed on this
+// stream before), or exactly (Q->atab == NULL)
+extern "C" hipError_t geoac_launch_postpass_freq(const GeoacDevParams* P, const GeoacFreqParams* Q, int rows, hipStream_t s){
+    if(rows < 2 || Q->n_extra < 1) return hipSuccess;
+    if(P->gtab || P->n_members > 1 || Q->n_extra > GEOAC_MAXF - 1) return hipErrorInvalidValue;
+    if(!Q->atab){
+        long long nbl = (long long)((P->n_cols_bound + 255) / 256) * (rows - 1);
+        if(P->pp_blocks > 0 && P->pp_blocks < nbl) nbl = P->pp_blocks;
+        if(nbl > 0x7fffffffLL) nbl = 0x7fffffffLL;
+        dim3 b(256), g((unsigned)nbl);
+        GEOAC_DISPATCH_EQ_STRAT(P, hipLaunchKernelGGL(k_postpass_freq_exact<EQ>, g, b, 0, s, *P, *Q, rows));
+        return hipGetLastError();
+    }
+    if(!P->atab) return hipErrorInvalidValue;
+    const int gy = (rows - 1 + GEOAC_PP_ROWS - 1) / GEOAC_PP_ROWS;
+    const unsigned lds = GEOAC_PP_ROWS * GEOAC_PF_THREADS * 20u;
+    dim3 b(GEOAC_PF_THREADS);
+    for(int gy0 = 0; gy0 < gy; gy0 += 65535){
+        dim3 g((unsigned)((P->n_cols_bound + GEOAC_PF_THREADS - 1) / GEOAC_PF_THREADS), (unsigned)(gy - gy0 > 65535 ? 65535 : gy - gy0));
+        GEOAC_DISPATCH_EQ_STRAT(P, hipLaunchKernelGGL(k_postpass_freq<EQ>, g, b, lds, s, *P, *Q, rows, gy0));
+    }
+    hipError_t e = hipGetLastError();
+    if(e != hipSuccess) return e;
+    dim3 gf(64), bf(256);
+    GEOAC_DISPATCH_EQ_STRAT(P, hipLaunchKernelGGL(k_ppfix_freq<EQ>, gf, bf, 0, s, *P, *Q));
+    return hipGetLastError();
+}
+extern "C" hipError_t geoac_launch_accum_freq(const GeoacDevParams* P, const GeoacFreqParams* Q, hipStream_t s){
+    if(Q->n_extra < 1) return hipSuccess;
+    dim3 b(256), g((unsigned)((P->n_cols_bound + 255) / 256), (unsigned)Q->n_extra);
+    hipLaunchKernelGGL(k_accum_freq, g, b, 0, s, *P, *Q);
+    return hipGetLastError();
+}
+extern "C" hipError_t geoac_launch_atten_col0(const double* rec, double* atten, long long n, hipStream_t s){
+    if(n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_atten_col0, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rec, atten, n);
+    return hipGetLastError();
+}

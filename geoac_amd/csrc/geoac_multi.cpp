@@ -76,6 +76,7 @@ int geoac_pool_fan_run(geoac_pool* p, int n_rays, const double* theta, const dou
     const size_t D = p->ctx.size();
     for(geoac_ctx* c : p->ctx){ int k = 1; if(geoac_get_members(c, &k) == GEOAC_OK && k > 1) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: ensembles are not available in the pool"); }
     for(geoac_ctx* c : p->ctx){ int k = 1; if(geoac_get_sources(c, &k) == GEOAC_OK && k > 1) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: a source set (geoac_set_sources) is not available in the pool"); }
+    for(geoac_ctx* c : p->ctx){ int k = 1; if(geoac_get_frequencies(c, &k) == GEOAC_OK && k > 1) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: a frequency set (geoac_set_frequencies) is not available in the pool"); }
     // the record stride comes from the contexts themselves (their defaults or whatever was set through the pool or through
     // geoac_pool_ctx): every context must write the same number of legs per ray in the same mode, or the groups would overlap
     geoac_params p0{};

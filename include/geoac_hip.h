@@ -178,6 +178,39 @@ int  geoac_get_eqset(geoac_ctx* ctx, int* eqset);
 int  geoac_set_sources(geoac_ctx* ctx, int n_src, const double* src);
 int  geoac_get_sources(geoac_ctx* ctx, int* n_src);
 
+/* frequency set: one geoac_fan_launch gives the Sutherland-Bass attenuation of every arrival at n_freq frequencies (a band, 0.05 - 5 Hz or so).
+ * Absorption is the only part of a fan's answer that depends on geoac_params.freq - paths, step counts, travel times, amplitudes and arrival
+ * geometry do not - and it is computed in the post-pass from the paths the integration has written: the fan is integrated once, the post-pass
+ * forms the attenuation increments of every path segment once per frequency, and the per-ray sums run once per frequency.
+ * GEOAC_EQ_2D, GEOAC_EQ_3D, GEOAC_EQ_GLOBAL only (a range-dependent set returns GEOAC_E_UNSUPPORTED); 1 <= n_freq <= GEOAC_MAX_FREQS, every
+ * frequency finite and > 0, duplicates allowed: anything else GEOAC_E_INVALID.
+ * freq_hz[0] becomes geoac_params.freq: the records are exactly those of a plain context with freq = freq_hz[0], all 32 fields, bit for bit.
+ * The attenuation table (geoac_fan_fetch_atten, geoac_fan_atten_dev) is [n_freq][n_rays][legs] f64, cumulative attenuation [dB] per (frequency,
+ * ray, leg) - the quantity GEOAC_REC_ATTEN holds; atten[0] holds the bits of the records' GEOAC_REC_ATTEN column, and atten[f] is bit-identical
+ * to the GEOAC_REC_ATTEN column of a plain context whose freq is freq_hz[f], for every (ray, leg) - legs that did not run included (0) - under every
+ * launch-plan option, whenever neither run reports GEOAC_FAN_ABS_FALLBACK.
+ *   - Fallback: when the fix-up list of the table post-pass overflows for any frequency the fan is repeated with the exact post-pass for ALL
+ *     frequencies and GEOAC_FAN_ABS_FALLBACK is set (sticky), as for a single frequency; atten[f] then equals the ABS_TABLE=0 single run.
+ *   - The absorption table serves the set only if EVERY frequency's table qualifies by the rule of a single one (at most a quarter of its entries
+ *     flagged); otherwise all frequencies, frequency 0 included, take the exact post-pass (geoac_abs_table_info then reports 0 entries) - a single
+ *     run at a frequency whose own table qualifies takes the table path, and agrees with the set to the table's tolerance instead of bit for bit.
+ * While n_freq > 1:
+ *   - geoac_set_params keeps the set (its freq field is ignored), geoac_get_params reports freq_hz[0];
+ *   - geoac_abs_table_info sums entries, flagged entries and fix-up segments over the frequencies' tables;
+ *   - total_steps, the record shapes and geoac_fan_fetch are unchanged; a new atmosphere upload keeps the set (the tables are rebuilt for it);
+ *   - an ensemble (K > 1: upload a single profile first), a source set (n_src > 1: set a single source first), sample capture
+ *     (GEOAC_MODE_WRITE_RAYS / _CAUSTICS), the eigenray searches, geoac_clone and the pool return GEOAC_E_UNSUPPORTED; the first two are checked here
+ *     and again at the launch (an upload or geoac_set_sources may come in between).
+ * n_freq == 1 sets geoac_params.freq = freq_hz[0] and leaves the mode: no extra kernel runs and no extra buffer is held; geoac_fan_fetch_atten then
+ * returns the records' GEOAC_REC_ATTEN column as [1][n_rays][legs]. */
+#define GEOAC_MAX_FREQS 16
+int  geoac_set_frequencies(geoac_ctx* ctx, int n_freq, const double* freq_hz);
+int  geoac_get_frequencies(geoac_ctx* ctx, int* n_freq);
+/* [n_freq][n_rays][legs] f64 of the last completed launch, to the host */
+int  geoac_fan_fetch_atten(geoac_ctx* ctx, double* atten_host);
+/* device pointer to the same table (valid after launch, ordered on the context's stream) */
+int  geoac_fan_atten_dev(geoac_ctx* ctx, void** dev_ptr, size_t* bytes);
+
 /* c [km/s], u, v [km/s], rho of the uploaded 1-D atmosphere at abscissa x, evaluated on the host (set-up / reporting only) */
 int  geoac_medium_1d(geoac_ctx* ctx, double x, double out[4]);
 
