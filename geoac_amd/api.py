@@ -28,6 +28,36 @@ class Params(ctypes.Structure):
                 ("mode", ctypes.c_int), ("sample_stride", ctypes.c_int), ("xy_limits", ctypes.c_double * 4)]
 
 
+class MapSpec(ctypes.Structure):
+    """geoac_map_spec (include/geoac_map.h): grid, filters and detection threshold of an arrival map"""
+    _fields_ = [("origin", ctypes.c_double * 2), ("step", ctypes.c_double * 2), ("n", ctypes.c_int * 2), ("wrap_lon", ctypes.c_int),
+                ("leg_min", ctypes.c_int), ("leg_max", ctypes.c_int), ("turn_min", ctypes.c_double), ("turn_max", ctypes.c_double),
+                ("detect_db", ctypes.c_double)]
+
+
+MAP_COUNT, MAP_TTIME_MIN, MAP_CEL_MAX, MAP_LEVEL_MAX, MAP_BEST = 0, 1, 2, 3, 4
+_MAP_LAYERS = (("count", MAP_COUNT, np.uint64), ("ttime_min", MAP_TTIME_MIN, np.float64), ("cel_max", MAP_CEL_MAX, np.float64),
+               ("level_max", MAP_LEVEL_MAX, np.float64), ("best", MAP_BEST, np.int64))
+
+
+def map_spec(origin, step, n, wrap_lon=False, leg_min=0, leg_max=2**31 - 1, turn_min=-np.inf, turn_max=np.inf, detect_db=np.nan):
+    """a MapSpec from plain values; one-axis grids (the 2-D set) may give scalars: axis 1 then is a single cell"""
+    origin, step, n = (list(np.atleast_1d(a)) for a in (origin, step, n))
+    if len(origin) == 1:
+        origin, step, n = origin + [0.0], step + [1.0], n + [1]
+    return MapSpec((ctypes.c_double * 2)(*[float(v) for v in origin]), (ctypes.c_double * 2)(*[float(v) for v in step]), (ctypes.c_int * 2)(*[int(v) for v in n]),
+                   1 if wrap_lon else 0, int(leg_min), int(leg_max), float(turn_min), float(turn_max), float(detect_db))
+
+
+def map_check(eqset, spec):
+    """geoac_map_check: host-only validation (no GPU needed); returns the cell count or raises GeoAcError"""
+    cells = ctypes.c_int64(0)
+    rc = load_library().geoac_map_check(int(eqset), ctypes.byref(spec), ctypes.byref(cells))
+    if rc:
+        raise GeoAcError(f"geoac_map_check: {load_library().geoac_strerror(rc).decode()}")
+    return int(cells.value)
+
+
 EIG_STRIDE = 16
 EIG = dict(RCVR=0, INDEX=1, BOUNCES=2, THETA=3, PHI=4, TTIME=5, CELERITY=6, AMP_DB=7, ATTEN_DB=8, INCL=9, BEARING=10, BACKAZ=11,
            AZDEV=12, NSMP=13, SMP0=14)
@@ -346,6 +376,45 @@ class FanContext:
                 raise GeoAcError(f"fetch_atten(out=): need a C-contiguous float64 array of shape {shape}")
         self._chk(self.lib.geoac_fan_fetch_atten(self._h, _p(att)))
         return att
+
+    # ---- arrival maps (include/geoac_map.h): the binning runs on the device; nothing is computed here ----
+    def _launch_members(self):
+        return self.n_sources * self.n_members
+
+    def fetch_level(self):
+        """level [dB] of every arrival of the last launch, (calc_amp ? 20 log10(AMP) : 0) - ATTEN per frequency: [M][F][n_rays][legs], NaN where the leg
+        wrote no row (M = n_sources * n_members, F = frequencies of the set)"""
+        lv = np.empty((self._launch_members(), self._n_freq, self.n_rays, self.params.bounces + 1))
+        self._chk(self.lib.geoac_fan_fetch_level(self._h, _p(lv)))
+        return lv
+
+    def map(self, spec=None, **kw):
+        """geoac_fan_map of the last launch: `spec` a MapSpec, or the arguments of map_spec().  Returns a dict of numpy arrays: count, ttime_min, cel_max
+        [M][n0][n1], level_max, best [M][F][n0][n1], outside [M], and detect [F][n0][n1] when detect_db is given.  May be called again with another
+        spec without a new launch."""
+        if spec is None:
+            spec = map_spec(**kw)
+        self._chk(self.lib.geoac_fan_map(self._h, ctypes.byref(spec)))
+        M, F, n0, n1 = (ctypes.c_int(0) for _ in range(4))
+        self._chk(self.lib.geoac_fan_map_shape(self._h, *[ctypes.byref(v) for v in (M, F, n0, n1)]))
+        M, F, n0, n1 = M.value, F.value, n0.value, n1.value
+        out = {}
+        for name, layer, dtype in _MAP_LAYERS:
+            a = np.empty((M, n0, n1) if layer < MAP_LEVEL_MAX else (M, F, n0, n1), dtype=dtype)
+            self._chk(self.lib.geoac_fan_map_fetch(self._h, layer, a.ctypes.data_as(ctypes.c_void_p)))
+            out[name] = a
+        out["outside"] = np.empty(M, dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_map_outside(self._h, out["outside"].ctypes.data_as(ctypes.c_void_p)))
+        if spec.detect_db == spec.detect_db:
+            out["detect"] = np.empty((F, n0, n1), dtype=np.uint32)
+            self._chk(self.lib.geoac_fan_map_fetch_detect(self._h, out["detect"].ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def map_timing(self):
+        """HIP-event time of the last map() on the context's stream [ms]"""
+        ms = ctypes.c_double(0)
+        self._chk(self.lib.geoac_fan_map_timing(self._h, ctypes.byref(ms)))
+        return ms.value
 
     def set_angles(self, theta_deg, phi_deg):
         th, ph = _arr(theta_deg), _arr(phi_deg)

@@ -21,6 +21,7 @@
 #include "../../include/geoac_probe.h"
 #include "../../include/geoac_host.h"
 #include "geoac_device.h"
+#include "geoac_map_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s);
@@ -223,6 +224,11 @@ struct geoac_ctx {
     std::vector<hipEvent_t> evf;                  // per epoch: the frequency post-pass has finished (k_accum_freq may start)
     int last_n_freq = 1;                          // of the last completed launch
     unsigned long long freq_fixup_segments = 0;   // last launch: (segment, frequency) pairs the extra frequencies' tables did not serve
+    // arrival maps (geoac_map.hip): map_gen is bumped by everything that invalidates a map - a launch, new angles, an atmosphere upload, geoac_set_sources,
+    // geoac_set_frequencies; launch_gen is its value when the last launch completed, so records, level table and maps are current while the two agree.
+    // map_state belongs to geoac_map.hip and stays NULL (nothing allocated, nothing launched) until the first geoac_fan_map / geoac_fan_fetch_level
+    unsigned long long map_gen = 1, launch_gen = 0;
+    void* map_state = nullptr;
     std::string err;
 };
 
@@ -413,6 +419,7 @@ int geoac_destroy(geoac_ctx* ctx){
     ctx->atmo_gen->store(~0ull);                                  // (clones of this context must not launch on its freed tables)
     hipSetDevice(ctx->device);
     if(ctx->stream) hipStreamSynchronize(ctx->stream);
+    if(ctx->map_state){ geoac_map_release(ctx->map_state); ctx->map_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->nrows[0], &ctx->nrows[1], &ctx->nrows[2], &ctx->legend[0], &ctx->legend[1], &ctx->legend[2],
@@ -513,6 +520,7 @@ static int upload_members(geoac_ctx* ctx, int K, int n, const double* x, const d
     if(!(ctx->prm.vert_limit == ctx->prm.vert_limit)) ctx->prm.vert_limit = x[n - 1];
     ctx->have_atmo = true;
     ctx->atmo_version++; ctx->atmo_gen->fetch_add(1);
+    ctx->map_gen++;
     ctx->ran = false;                             // (the probes launch with the tables of the last fan: not after a new upload)
     const int K_was = ctx->n_members;
     ctx->n_members = K;
@@ -569,6 +577,7 @@ int geoac_set_sources(geoac_ctx* ctx, int n_src, const double* src){
                     std::to_string(GEOAC_MAX_MEMBERS) + " members of a launch");
     ctx->prm.src[0] = src[0]; ctx->prm.src[1] = src[1]; ctx->prm.src[2] = src[2];
     ctx->n_src = n_src;
+    ctx->map_gen++;
     if(n_src > 1) ctx->sources.assign(src, src + 3 * (size_t)n_src); else ctx->sources.clear();
     if(ctx->have_angles && ctx->layout_members != n_src * ctx->n_members) return layout_angles(ctx);       // (the slot layout depends on the number of members)
     return GEOAC_OK;
@@ -594,6 +603,7 @@ int geoac_set_frequencies(geoac_ctx* ctx, int n_freq, const double* freq_hz){
         return fail(ctx, GEOAC_E_UNSUPPORTED, "set_frequencies: not available while a source set is active (geoac_set_sources); set a single source first");
     ctx->prm.freq = freq_hz[0];
     ctx->n_freq = n_freq;
+    ctx->map_gen++;
     if(n_freq > 1) ctx->freqs.assign(freq_hz, freq_hz + n_freq);
     else {                                                        // leaves the mode: nothing of the family is held
         ctx->freqs.clear();
@@ -666,6 +676,7 @@ int geoac_upload_atmo_3d(geoac_ctx* ctx, int nx, int ny, int nz, const double* x
     for(int q = 0; q < 4; q++) if(!(ctx->prm.xy_limits[q] == ctx->prm.xy_limits[q])) ctx->prm.xy_limits[q] = ext[q];
     ctx->have_grid = true; ctx->have_atmo = true;
     ctx->atmo_version++; ctx->atmo_gen->fetch_add(1);
+    ctx->map_gen++;
     ctx->ran = false;                             // (the probes launch with the tables of the last fan: not after a new upload)
     return GEOAC_OK;
 }
@@ -723,6 +734,7 @@ int geoac_set_params(geoac_ctx* ctx, const geoac_params* p){
 int geoac_fan_set_angles(geoac_ctx* ctx, int n_rays, const double* theta_deg, const double* phi_deg){
     if(!ctx || n_rays <= 0 || !theta_deg || !phi_deg) return fail(ctx, GEOAC_E_INVALID, "fan_set_angles: bad arguments");
     ctx->ang_th.assign(theta_deg, theta_deg + n_rays); ctx->ang_ph.assign(phi_deg, phi_deg + n_rays);
+    ctx->map_gen++;
     return layout_angles(ctx);
 }
 
@@ -1467,8 +1479,10 @@ int geoac_fan_launch(geoac_ctx* ctx){
                                           "the clone's views of the source's tables are no longer valid; clone again");
     struct Guard { Guard(){ g_launching.fetch_add(1); } ~Guard(){ if(g_launching.fetch_sub(1) == 1) g_deferred.drain_if_any(); } } guard;
     // at most one repeat per plan feature that can be withdrawn (sub-epochs, absorption table): a loop, not a recursion
+    ctx->map_gen++;                               // (the record table is about to be rewritten: maps of the launch before are gone)
     for(int attempt = 0; attempt < 3; attempt++){
         const int rc = fan_launch_once(ctx);
+        if(rc == GEOAC_OK) ctx->launch_gen = ctx->map_gen;
         if(rc != GEOAC_RETRY) return rc;
         ctx->launch_repeats++;
     }
@@ -1556,6 +1570,20 @@ int geoac_fan_fetch_atten(geoac_ctx* ctx, double* atten_host){
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return GEOAC_OK;
 }
+
+// what geoac_map.hip needs of a context (geoac_map_int.h): the tables of the last completed launch and their shapes, nothing of the launch plan
+int geoac_map_view(geoac_ctx* ctx, GeoacMapView* v){
+    if(!ctx || !v) return GEOAC_E_INVALID;
+    v->eqset = ctx->eqset; v->device = ctx->device; v->stream = (void*)ctx->stream;
+    v->gen = ctx->map_gen;
+    v->fresh = (ctx->ran && ctx->launch_gen == ctx->map_gen && ctx->n_freq == ctx->last_n_freq) ? 1 : 0;
+    v->rec = (const double*)ctx->rec.p;
+    v->M = ctx->lastP.n_members; v->F = ctx->last_n_freq; v->n_rays = ctx->n_rays; v->legs = ctx->legs; v->calc_amp = ctx->lastP.calc_amp;
+    v->atten = v->F > 1 ? (const double*)ctx->fatten.p : nullptr;
+    v->state = &ctx->map_state;
+    return GEOAC_OK;
+}
+int geoac_map_fail(geoac_ctx* ctx, int code, const char* msg){ return fail(ctx, code, msg); }
 
 int geoac_fan_sample_count(geoac_ctx* ctx, int64_t* n){
     if(!ctx || !n || !ctx->ran) return GEOAC_E_INVALID;
