@@ -58,6 +58,31 @@ def map_check(eqset, spec):
     return int(cells.value)
 
 
+class StationSpec(ctypes.Structure):
+    """geoac_station_spec (include/geoac_stations.h): lattice of the launch angles, filters and list length of a station search"""
+    _fields_ = [("n_theta", ctypes.c_int), ("n_phi", ctypes.c_int), ("phi_periodic", ctypes.c_int), ("leg_min", ctypes.c_int), ("leg_max", ctypes.c_int),
+                ("turn_tol", ctypes.c_double), ("edge_max", ctypes.c_double), ("cap", ctypes.c_int)]
+
+
+STA_STRIDE = 16
+STA = dict(LEG=0, TRI=1, RAY0=2, ORIENT=3, W0=4, W1=5, W2=6, THETA=7, PHI=8, TTIME=9, CELERITY=10, TURN=11, INCL=12, BACKAZ=13)
+
+
+def station_spec(n_theta, n_phi, phi_periodic=False, leg_min=0, leg_max=2**31 - 1, turn_tol=np.inf, edge_max=np.inf, cap=16):
+    """a StationSpec from plain values"""
+    return StationSpec(int(n_theta), int(n_phi), 1 if phi_periodic else 0, int(leg_min), int(leg_max), float(turn_tol), float(edge_max), int(cap))
+
+
+def station_check(eqset, spec, n_rays, n_sta):
+    """geoac_station_check: host-only validation (no GPU needed); raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_station_fault.restype = ctypes.c_char_p
+    rc = lib.geoac_station_check(int(eqset), ctypes.byref(spec), int(n_rays), int(n_sta))
+    if rc:
+        fault = lib.geoac_station_fault(int(eqset), ctypes.byref(spec), int(n_rays), int(n_sta))
+        raise GeoAcError(f"geoac_station_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
+
+
 EIG_STRIDE = 16
 EIG = dict(RCVR=0, INDEX=1, BOUNCES=2, THETA=3, PHI=4, TTIME=5, CELERITY=6, AMP_DB=7, ATTEN_DB=8, INCL=9, BEARING=10, BACKAZ=11,
            AZDEV=12, NSMP=13, SMP0=14)
@@ -414,6 +439,30 @@ class FanContext:
         """HIP-event time of the last map() on the context's stream [ms]"""
         ms = ctypes.c_double(0)
         self._chk(self.lib.geoac_fan_map_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # ---- station arrivals (include/geoac_stations.h): search and interpolation run on the device; nothing is computed here ----
+    def stations(self, spec=None, sta=None, **kw):
+        """geoac_fan_stations of the last launch: `spec` a StationSpec, or the arguments of station_spec(); sta [n_sta][2] in the map's axes (lat, lon
+        [deg] / x, y [km]).  Returns hits [M][n_sta] u32 (the true count, may exceed cap), rows [M][n_sta][cap][STA_STRIDE] (columns STA) and level
+        [M][n_sta][cap][F].  May be called again with another spec or other stations without a new launch."""
+        if spec is None:
+            spec = station_spec(**kw)
+        sta = _arr(sta)
+        if sta.ndim != 2 or sta.shape[1] != 2:
+            raise GeoAcError(f"stations: sta must have shape [n_sta][2] (got {sta.shape})")
+        self._chk(self.lib.geoac_fan_stations(self._h, ctypes.byref(spec), len(sta), _p(sta)))
+        M, F, R, cap = (ctypes.c_int(0) for _ in range(4))
+        self._chk(self.lib.geoac_fan_stations_shape(self._h, *[ctypes.byref(v) for v in (M, F, R, cap)]))
+        M, F, R, cap = M.value, F.value, R.value, cap.value
+        hits, rows, level = np.empty((M, R), dtype=np.uint32), np.empty((M, R, cap, STA_STRIDE)), np.empty((M, R, cap, F))
+        self._chk(self.lib.geoac_fan_stations_fetch(self._h, hits.ctypes.data_as(ctypes.c_void_p), _p(rows), _p(level)))
+        return hits, rows, level
+
+    def stations_timing(self):
+        """HIP-event time of the last stations() on the context's stream [ms]"""
+        ms = ctypes.c_double(0)
+        self._chk(self.lib.geoac_fan_stations_timing(self._h, ctypes.byref(ms)))
         return ms.value
 
     def set_angles(self, theta_deg, phi_deg):

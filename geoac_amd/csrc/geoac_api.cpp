@@ -22,6 +22,7 @@
 #include "../../include/geoac_host.h"
 #include "geoac_device.h"
 #include "geoac_map_int.h"
+#include "geoac_stations_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s);
@@ -229,6 +230,7 @@ struct geoac_ctx {
     // map_state belongs to geoac_map.hip and stays NULL (nothing allocated, nothing launched) until the first geoac_fan_map / geoac_fan_fetch_level
     unsigned long long map_gen = 1, launch_gen = 0;
     void* map_state = nullptr;
+    void* sta_state = nullptr;                    // station arrivals (geoac_stations.hip): NULL until the first geoac_fan_stations
     std::string err;
 };
 
@@ -420,6 +422,7 @@ int geoac_destroy(geoac_ctx* ctx){
     hipSetDevice(ctx->device);
     if(ctx->stream) hipStreamSynchronize(ctx->stream);
     if(ctx->map_state){ geoac_map_release(ctx->map_state); ctx->map_state = nullptr; }
+    if(ctx->sta_state){ geoac_sta_release(ctx->sta_state); ctx->sta_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->nrows[0], &ctx->nrows[1], &ctx->nrows[2], &ctx->legend[0], &ctx->legend[1], &ctx->legend[2],
@@ -1584,6 +1587,15 @@ int geoac_map_view(geoac_ctx* ctx, GeoacMapView* v){
     return GEOAC_OK;
 }
 int geoac_map_fail(geoac_ctx* ctx, int code, const char* msg){ return fail(ctx, code, msg); }
+
+// ... and geoac_stations.hip (geoac_stations_int.h): the same view and the caller's launch angles in ray order
+int geoac_sta_view(geoac_ctx* ctx, GeoacStaView* v){
+    int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
+    if(rc) return rc;
+    v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
+    v->state = &ctx->sta_state;
+    return GEOAC_OK;
+}
 
 int geoac_fan_sample_count(geoac_ctx* ctx, int64_t* n){
     if(!ctx || !n || !ctx->ran) return GEOAC_E_INVALID;
