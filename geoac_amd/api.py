@@ -83,6 +83,41 @@ def station_check(eqset, spec, n_rays, n_sta):
         raise GeoAcError(f"geoac_station_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
 
 
+class TubeSpec(ctypes.Structure):
+    """geoac_tube_spec (include/geoac_tubemap.h): the grid of a MapSpec, the lattice and triangle filters of a StationSpec, the band on a hit's
+    interpolated turning height and the detection threshold of a tube map"""
+    _fields_ = [("origin", ctypes.c_double * 2), ("step", ctypes.c_double * 2), ("n", ctypes.c_int * 2), ("wrap_lon", ctypes.c_int),
+                ("n_theta", ctypes.c_int), ("n_phi", ctypes.c_int), ("phi_periodic", ctypes.c_int), ("leg_min", ctypes.c_int), ("leg_max", ctypes.c_int),
+                ("turn_tol", ctypes.c_double), ("edge_max", ctypes.c_double), ("turn_min", ctypes.c_double), ("turn_max", ctypes.c_double),
+                ("detect_db", ctypes.c_double)]
+
+
+TUBE = dict(COUNT=0, TTIME_MIN=1, CEL_MAX=2, LEVEL_MAX=3, BEST=4)
+TUBE_MAX_SPAN, TUBE_COOP_MIN = 1 << 20, 32
+_TUBE_LAYERS = (("count", TUBE["COUNT"], np.uint64), ("ttime_min", TUBE["TTIME_MIN"], np.float64), ("cel_max", TUBE["CEL_MAX"], np.float64),
+                ("level_max", TUBE["LEVEL_MAX"], np.float64), ("best", TUBE["BEST"], np.int64))
+
+
+def tube_spec(origin, step, n, n_theta, n_phi, edge_max, wrap_lon=False, phi_periodic=False, leg_min=0, leg_max=2**31 - 1, turn_tol=np.inf,
+              turn_min=-np.inf, turn_max=np.inf, detect_db=np.nan):
+    """a TubeSpec from plain values (edge_max has no default: it must be finite, it bounds the cells a landing triangle can cover)"""
+    return TubeSpec((ctypes.c_double * 2)(*[float(v) for v in origin]), (ctypes.c_double * 2)(*[float(v) for v in step]), (ctypes.c_int * 2)(*[int(v) for v in n]),
+                    1 if wrap_lon else 0, int(n_theta), int(n_phi), 1 if phi_periodic else 0, int(leg_min), int(leg_max), float(turn_tol), float(edge_max),
+                    float(turn_min), float(turn_max), float(detect_db))
+
+
+def tube_check(eqset, spec, n_rays):
+    """geoac_tube_check: host-only validation (no GPU needed); returns the cell count or raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_tube_fault.restype = ctypes.c_char_p
+    cells = ctypes.c_int64(0)
+    rc = lib.geoac_tube_check(int(eqset), ctypes.byref(spec), int(n_rays), ctypes.byref(cells))
+    if rc:
+        fault = lib.geoac_tube_fault(int(eqset), ctypes.byref(spec), int(n_rays))
+        raise GeoAcError(f"geoac_tube_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
+    return int(cells.value)
+
+
 EIG_STRIDE = 16
 EIG = dict(RCVR=0, INDEX=1, BOUNCES=2, THETA=3, PHI=4, TTIME=5, CELERITY=6, AMP_DB=7, ATTEN_DB=8, INCL=9, BEARING=10, BACKAZ=11,
            AZDEV=12, NSMP=13, SMP0=14)
@@ -464,6 +499,39 @@ class FanContext:
         ms = ctypes.c_double(0)
         self._chk(self.lib.geoac_fan_stations_timing(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # ---- tube maps (include/geoac_tubemap.h): the rasteriser runs on the device; nothing is computed here ----
+    def tubemap(self, spec=None, **kw):
+        """geoac_fan_tubemap of the last launch: `spec` a TubeSpec, or the arguments of tube_spec().  Returns a dict of numpy arrays: count, ttime_min,
+        cel_max [M][n0][n1], level_max, best [M][F][n0][n1], and detect [F][n0][n1] when detect_db is given.  May be called again with another spec
+        without a new launch."""
+        if spec is None:
+            spec = tube_spec(**kw)
+        self._chk(self.lib.geoac_fan_tubemap(self._h, ctypes.byref(spec)))
+        M, F, n0, n1 = (ctypes.c_int(0) for _ in range(4))
+        self._chk(self.lib.geoac_fan_tubemap_shape(self._h, *[ctypes.byref(v) for v in (M, F, n0, n1)]))
+        M, F, n0, n1 = M.value, F.value, n0.value, n1.value
+        out = {}
+        for name, layer, dtype in _TUBE_LAYERS:
+            a = np.empty((M, n0, n1) if layer < TUBE["LEVEL_MAX"] else (M, F, n0, n1), dtype=dtype)
+            self._chk(self.lib.geoac_fan_tubemap_fetch(self._h, layer, a.ctypes.data_as(ctypes.c_void_p)))
+            out[name] = a
+        if spec.detect_db == spec.detect_db:
+            out["detect"] = np.empty((F, n0, n1), dtype=np.uint32)
+            self._chk(self.lib.geoac_fan_tubemap_fetch_detect(self._h, out["detect"].ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def tubemap_timing(self):
+        """HIP-event time of the last tubemap() on the context's stream [ms]"""
+        ms = ctypes.c_double(0)
+        self._chk(self.lib.geoac_fan_tubemap_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def tubemap_stats(self):
+        """work counters of the last tubemap(): triangles that proposed cell centres, those walked cooperatively by a wave, centres tested"""
+        st = np.zeros(4, dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_tubemap_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
+        return dict(triangles=int(st[0]), cooperative=int(st[1]), candidates=int(st[2]))
 
     def set_angles(self, theta_deg, phi_deg):
         th, ph = _arr(theta_deg), _arr(phi_deg)

@@ -23,6 +23,7 @@
 #include "geoac_device.h"
 #include "geoac_map_int.h"
 #include "geoac_stations_int.h"
+#include "geoac_tubemap_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s);
@@ -231,6 +232,7 @@ struct geoac_ctx {
     unsigned long long map_gen = 1, launch_gen = 0;
     void* map_state = nullptr;
     void* sta_state = nullptr;                    // station arrivals (geoac_stations.hip): NULL until the first geoac_fan_stations
+    void* tube_state = nullptr;                   // tube maps (geoac_tubemap.hip): NULL until the first geoac_fan_tubemap
     std::string err;
 };
 
@@ -423,6 +425,7 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->stream) hipStreamSynchronize(ctx->stream);
     if(ctx->map_state){ geoac_map_release(ctx->map_state); ctx->map_state = nullptr; }
     if(ctx->sta_state){ geoac_sta_release(ctx->sta_state); ctx->sta_state = nullptr; }
+    if(ctx->tube_state){ geoac_tube_release(ctx->tube_state); ctx->tube_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->nrows[0], &ctx->nrows[1], &ctx->nrows[2], &ctx->legend[0], &ctx->legend[1], &ctx->legend[2],
@@ -1594,6 +1597,15 @@ int geoac_sta_view(geoac_ctx* ctx, GeoacStaView* v){
     if(rc) return rc;
     v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
     v->state = &ctx->sta_state;
+    return GEOAC_OK;
+}
+
+// ... and geoac_tubemap.hip (geoac_tubemap_int.h): the same again, with the tube map's slot
+int geoac_tube_view(geoac_ctx* ctx, GeoacTubeView* v){
+    int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
+    if(rc) return rc;
+    v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
+    v->state = &ctx->tube_state;
     return GEOAC_OK;
 }
 

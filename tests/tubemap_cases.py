@@ -1,0 +1,116 @@
+"""The cases of the tube-map tests: launch set-ups and grid literals, shared by tests/test_tubemap_host.py (which proves on the CPU oracle's
+records that every grid meets the non-vacuity conditions) and tests/test_gpu_tubemap.py (which runs them on the device).  Launches are those of
+the map cases (tests/map_cases.py) over the 13 x 9 lattice fans of tests/station_cases.py with one bounce.  Grid extents, bands and edge_max were
+chosen from the oracle's landing points; they are literals, not derived from the code under test."""
+import numpy as np
+
+import harness as H
+import map_cases as MC
+import map_reference as MR
+import station_cases as SC
+import tubemap_reference as TR
+from test_gpu_ensemble import _raw_members
+from test_gpu_freqs import FREQS
+
+ONE_BOUNCE = dict(bounces=1, calc_amp=1)
+# the full-circle lattice of the column-wrap case: 13 inclinations x 9 azimuths 40 degrees apart, -180 .. 140, the last column neighbours the first
+CIRCLE_LATTICE = dict(theta_min=3.0, theta_max=39.0, theta_step=3.0, phi_min=-180.0, phi_max=140.0, phi_step=40.0)
+WRAP_SRC = (0.0, 30.0, 179.0)
+# two sources whose fans land on one grid: the ground source of the plain cases and one 20 km up, 1.5 degrees north and 2 degrees west of it
+TUBE_SOURCES = np.array([[0.0, 30.0, 0.0], [20.0, 31.5, -2.0]])
+
+LAUNCHES = {
+    "3d": dict(kind="plain", eq=H.EQ_3D, params=ONE_BOUNCE),
+    "global": dict(kind="plain", eq=H.EQ_GLOBAL, params=ONE_BOUNCE),
+    "3drd": dict(kind="3drd", eq=H.EQ_3D_RNGDEP, params=dict(bounces=1, calc_amp=1, mode=0, src=(0.0, 0.0, 0.0))),
+    "globalrd": dict(kind="globalrd", eq=H.EQ_GLOBAL_RNGDEP, params=dict(bounces=1, calc_amp=1, mode=0, src=(0.0, 31.0, 0.0))),
+    "ensemble3": dict(kind="ensemble", eq=H.EQ_GLOBAL, params=ONE_BOUNCE),
+    "sources2x2": dict(kind="sources", eq=H.EQ_GLOBAL, sources=TUBE_SOURCES, n_prof=2, params=ONE_BOUNCE),
+    "freqs3": dict(kind="freqs", eq=H.EQ_GLOBAL, freqs=FREQS[:3], params=ONE_BOUNCE),
+    "circle": dict(kind="plain", eq=H.EQ_GLOBAL, params=dict(ONE_BOUNCE, src=WRAP_SRC), lattice=CIRCLE_LATTICE),
+}
+
+# grids (at most 32 x 48 cells).  The westward fan from (30, 0) lands at lat 27.8 .. 32.1, lon -6.1 .. -2.1 on leg 0 and lat 25.5 .. 34.1,
+# lon -12.5 .. -4.1 on leg 1; the Cartesian one at x -540 .. -205, |y| < 309 km and x -1081 .. -410, |y| < 617 km
+GRID_GLOBAL = dict(origin=(25.0, -10.0), step=(0.375, 0.25), n=(24, 40), edge_max=3.0)
+GRID_3D = dict(origin=(-900.0, -450.0), step=(37.5, 30.0), n=(24, 30), edge_max=300.0)
+GRID_3DRD = dict(origin=(-620.0, -300.0), step=(17.5, 25.0), n=(24, 24), edge_max=300.0)
+GRID_GLOBALRD = dict(origin=(28.0, -6.0), step=(0.2, 0.16), n=(25, 25), edge_max=3.0)
+GRID_2SRC = dict(origin=(25.5, -11.5), step=(0.3, 0.3), n=(28, 32), edge_max=3.0)                       # the two sources of TUBE_SOURCES
+# lon -180 .. -168: the fan from lon 179 lands at 169.6 .. 187.3 (the state's longitude is continuous), its part beyond 180 is on the grid modulo 360
+GRID_CIRCLE = dict(origin=(20.0, -180.0), step=(0.625, 0.25), n=(32, 48), edge_max=8.0, wrap_lon=True, phi_periodic=True)
+GRID_FINE = dict(origin=(28.0, -6.0), step=(0.0625, 0.0625), n=(32, 48), edge_max=3.0)                  # cells several times smaller than the triangles
+GRID_COARSE = dict(origin=(25.5, -11.5), step=(1.5, 1.5), n=(6, 7), edge_max=3.0)                       # cells larger than most triangles
+GRID_HALF_OFF = dict(origin=(28.0, -5.5), step=(0.25, 0.25), n=(24, 24), edge_max=3.0)                  # the landing area ends inside the grid
+
+CASES = {
+    "3d": dict(launch="3d", spec=dict(GRID_3D, detect_db=MC.DETECT_AMP)),
+    "global": dict(launch="global", spec=dict(GRID_GLOBAL, detect_db=MC.DETECT_AMP)),
+    "3drd": dict(launch="3drd", spec=dict(GRID_3DRD, detect_db=MC.DETECT_AMP)),
+    "globalrd": dict(launch="globalrd", spec=dict(GRID_GLOBALRD, detect_db=MC.DETECT_AMP)),
+    "ensemble3": dict(launch="ensemble3", spec=dict(GRID_GLOBAL, detect_db=MC.DETECT_AMP)),
+    "sources2x2": dict(launch="sources2x2", spec=dict(GRID_2SRC, detect_db=MC.DETECT_AMP)),
+    "freqs3": dict(launch="freqs3", spec=dict(GRID_GLOBAL, detect_db=-80.0)),
+    "circle-wrap": dict(launch="circle", spec=dict(GRID_CIRCLE)),
+    "fine": dict(launch="global", spec=dict(GRID_FINE), cooperative=True),
+    "coarse": dict(launch="global", spec=dict(GRID_COARSE)),
+    "half-off": dict(launch="global", spec=dict(GRID_HALF_OFF)),
+    "leg-band": dict(launch="global", spec=dict(GRID_GLOBAL, leg_min=1, leg_max=1)),
+    "turn-band": dict(launch="global", spec=dict(GRID_GLOBAL, turn_min=60.0, turn_max=np.inf)),      # the thermospheric family alone
+    "edge-max": dict(launch="global", spec=dict(GRID_GLOBAL, edge_max=2.0, turn_tol=20.0)),          # removes the long triangles
+}
+
+
+def lattice_of(launch):
+    kw = launch.get("lattice") or (SC.PARITY_LATTICE_RD if launch["kind"] in ("3drd", "globalrd") else SC.PARITY_LATTICE)
+    return SC.lattice(**kw)
+
+
+def profiles_of(launch):
+    """raw profile columns of the launch's members (None: ToyAtmo itself)"""
+    if launch["kind"] == "ensemble":
+        return _raw_members()
+    if launch["kind"] == "sources" and launch["n_prof"] > 1:
+        return _raw_members()[:launch["n_prof"]]
+    return [None]
+
+
+def spec_of(case, nt, nph, **overrides):
+    return TR.spec(n_theta=nt, n_phi=nph, **dict(case["spec"], **overrides))
+
+
+def oracle_tables(launch, tmpdir):
+    """the launch on the CPU oracle: rec [M][n_rays][legs][32], level [M][F][n_rays][legs] (numpy's log10), angles, lattice shape"""
+    eq, kind, prm = launch["eq"], launch["kind"], launch["params"]
+    th, ph, nt, nph = lattice_of(launch)
+    cfg = dict(bounces=prm["bounces"], calc_amp=bool(prm["calc_amp"]))
+    if "src" in prm:
+        cfg["src"] = prm["src"]
+    recs, atten = [], None
+
+    def oracle(raw):
+        O = H.Oracle(eq, H.TOYATMO if raw is None else None)
+        if raw is not None:
+            O.load_arrays(*raw)
+        return O
+
+    if kind in ("plain", "ensemble"):
+        for raw in profiles_of(launch):
+            recs.append(oracle(raw).fan(H.make_cfg(eq, **cfg), th, ph)[1])
+    elif kind == "sources":
+        for src in launch["sources"]:
+            for raw in profiles_of(launch):
+                recs.append(oracle(raw).fan(H.make_cfg(eq, src=tuple(src), **cfg), th, ph)[1])
+    elif kind == "freqs":
+        O = oracle(None)
+        per_f = [O.fan(H.make_cfg(eq, freq=f, **cfg), th, ph)[1] for f in launch["freqs"]]
+        recs.append(per_f[0])
+        atten = np.stack([r[:, :, H.REC["ATTEN"]] for r in per_f])
+    else:
+        O = H.Oracle(eq, met=None)
+        O.load_grid(*MC.write_grid(kind, str(tmpdir)))
+        recs.append(O.fan(H.make_cfg(eq, **cfg), th, ph)[1])
+    rec = np.stack(recs)
+    if atten is None:
+        atten = rec[0, :, :, H.REC["ATTEN"]][None]
+    return rec, MR.level_numpy(rec, atten, prm["calc_amp"]), th, ph, nt, nph
