@@ -38,6 +38,9 @@
 #ifndef GEOAC_RCPC
 #define GEOAC_RCPC 1                     // 1/r and 1/cos(lat) of stages 1-3 by a Newton step from stage 0's values (global_base); 0: a fresh seed per stage (A/B)
 #endif
+#ifndef GEOAC_RCPC_EMAX
+#define GEOAC_RCPC_EMAX 1.0e-5          // largest |1 - cos(lat) / cos(lat of stage 0)| the Newton step of GEOAC_RCPC is trusted with (its cube, 1e-15 - up to 9 ulp -, is the error left)
+#endif
 #ifndef GEOAC_AB
 #define GEOAC_AB 0                      // 1: A/B build (`make AB=1`) - also holds the diagnostic kernels the launch plan never selects
 #endif
@@ -358,14 +361,18 @@ DEVINL void global_base(TabPtr tab, const GeoacDevParams& P, int& seg, double* r
     const double nn  = __builtin_fma(n0, n0, __builtin_fma(n1, n1, n2 * n2));
     const double inm0 = frsq(nn);
 #if GEOAC_RCPC
-    // 1/r and 1/cos(lat) of stages 1-3 by ONE third-order Newton step from the step's stage-0 values (r and cos(lat) move by < 1e-5 of themselves within a step: e^3 < 1e-15),
-    // not from a fresh transcendental seed (17 issue cycles each against 4.4 for a multiply-add)
+    // 1/r and 1/cos(lat) of stages 1-3 by ONE third-order Newton step from the step's stage-0 values, not from a fresh transcendental seed (17 issue cycles
+    // each against 4.4 for a multiply-add).  The step leaves a relative error of e^3, e = 1 - x / x0.  r moves by at most ds / r < 1e-5 of itself within a
+    // step (ds <= 0.05 km: set_ds), always.  cos(lat) moves by e2 = tan(lat) dlat: below 1e-5 up to |lat| ~ 52 degrees, but 6e-2 for a ray that passes 0.004 degrees from a pole, and
+    // beyond 1 where it crosses the pole and cos(lat) changes sign.  So a lane whose |e2| exceeds GEOAC_RCPC_EMAX takes a fresh reciprocal for that stage
+    // (e^3 <= 1e-15 for every other lane; away from the poles no lane takes the branch and the bits are those of the unguarded step).  !(<=): a NaN goes there too.
     double ir, ico;
     if(ROT0 || first){ ir = frcp(r); ico = frcp(cth); rcp0[0] = ir; rcp0[1] = ico; }     // (first: k_rk4_duo rolls all four stages into one loop - stage 0 by a run-time flag)
     else {
         const double e1 = __builtin_fma(-r, rcp0[0], 1.0), e2 = __builtin_fma(-cth, rcp0[1], 1.0);
         ir = __builtin_fma(rcp0[0], __builtin_fma(e1, e1, e1), rcp0[0]);
         ico = __builtin_fma(rcp0[1], __builtin_fma(e2, e2, e2), rcp0[1]);
+        if(__builtin_expect(!(fabs(e2) <= GEOAC_RCPC_EMAX), 0)) ico = frcp(cth);
     }
 #else
     const double ir  = frcp(r);

@@ -1,7 +1,9 @@
 """Generates tests/golden/*.npz from the COMPILED, UNMODIFIED reference (oracle/_ref/libref_*.so, built
 by oracle/Makefile from /root/reference).  Run here only (the reference does not travel):
 
-    make -C oracle all && python tests/golden/make_golden.py
+    make -C oracle all && python tests/golden/make_golden.py            # {global,3d,2d}_small.npz; `rngdep`, `globalrd`: the grid sets'
+    python tests/golden/make_golden.py polar                            # global_polar.npz (3 minutes on one core)
+    python tests/golden/make_golden.py globalrd_polar                   # globalrd_polar.npz (2 minutes)
 
 The fixtures are data: launch angles + configuration in, full-precision arrival records / samples /
 probe values out.  tests/test_oracle_golden.py pins the plain-C oracle to them bit for bit;
@@ -165,8 +167,123 @@ def main_globalrd():
     print("globalrd ->", path, os.path.getsize(path) // 1024, "KiB;", os.path.getsize(RD.GRID_GLOBAL_NPZ) // 1024, "KiB grid")
 
 
+# ---- stratified Global set near the poles (tests/test_gpu_polar.py) ----
+# name -> source (z, lat, lon), azimuth of the poleward direction.  The azimuths of a fan are POLAR_AZ + that direction: rays that pass the pole at
+# 0.004 .. 0.05 degrees on either side, and rays that leave sideways and away.  85.5 N: where a stage's 1/cos(lat) taken from the step's first stage was last quoted as harmless; -89: cos as at 89, sin and tan mirrored.
+POLAR_SOURCES = {"n89": ((0.0, 89.0, 0.0), 0.0), "n855": ((0.0, 85.5, 20.0), 0.0), "s89": ((0.0, -89.0, 0.0), 180.0)}
+POLAR_TH = [2.0, 8.0, 14.0, 20.0, 26.0]
+POLAR_AZ = [-3.0, -2.0, -1.0, -0.25, 0.25, 1.0, 2.0, 3.0, 10.0, 45.0, 90.0, 180.0]
+POLAR_SENS_EPS = 1e-12
+# Azimuth 0 - the ray aimed AT the pole - was dropped from all three fans: it fails the conditioning assertion below on the compiled reference.  ToyAtmo's
+# zonal wind carries it past the pole at a distance far below 0.004 degrees, and the reference's own arrival longitude then answers theta (1 + 1e-12) with
+# 2.3e-9 rad where it is -1.8e-3 rad (89 N and 89 S, theta 26, leg 1: 1.3e-6 by compare_records' measure) and its launch-angle derivatives with 4.9e-7
+# (85.5 N, theta 2): no arithmetic but the reference's own bit pattern follows it to 1e-6 there.  Rays over the pole stay in the tests that need no
+# reference: tests/test_gpu_polar.py adds them to the bit-identity and Hamiltonian checks, the straight-ray cases of tests/test_oracle_known_answers.py hold one.
+
+
+def polar_fan(poleward):
+    th = np.array([t for a in POLAR_AZ for t in POLAR_TH])
+    ph = np.array([poleward + a for a in POLAR_AZ for t in POLAR_TH])
+    return th, ph
+
+
+def main_polar():
+    """global_polar.npz: per source and CalcAmp setting the compiled reference's records and step total, and `sens`: how far each compared field of each
+    arrival moves IN THE REFERENCE when theta is multiplied by 1 + 1e-12 (parity.field_errors: compare_records' own measures).  4 x sens <= 1e-6 is
+    asserted for every field of every arrival - the 1e-6 comparison of the HIP path needs no exemption list on these fans."""
+    from parity import field_errors
+    eq = H.EQ_GLOBAL
+    R, O = H.RefShim(eq), H.Oracle(eq)
+    out = {"names": np.array(list(POLAR_SOURCES)), "az_rel": np.array(POLAR_AZ), "sens_eps": np.float64(POLAR_SENS_EPS)}
+    for name, (src, poleward) in POLAR_SOURCES.items():
+        th, ph = polar_fan(poleward)
+        out[f"{name}_src"] = np.array(src); out[f"{name}_theta"] = th; out[f"{name}_phi"] = ph
+        for amp in (1, 0):
+            cfg = H.make_cfg(eq, bounces=2, calc_amp=bool(amp), src=src)
+            steps, rec, _, _ = R.fan(cfg, th, ph)
+            so, ro, _, _ = O.fan(cfg, th, ph)
+            assert so == steps and np.array_equal(ro, rec), f"{name} amp{amp}: the oracle's records differ from the compiled reference's"
+            sp, rp, _, _ = R.fan(cfg, th * (1.0 + POLAR_SENS_EPS), ph)
+            for f in ("VALID", "STEPS", "BROKE"):
+                assert np.array_equal(rp[..., H.REC[f]], rec[..., H.REC[f]]), f"{name} amp{amp}: {f} moves with theta (1 + {POLAR_SENS_EPS:g})"
+            E = 18 if amp else 6
+            fe = field_errors(rp, rec, E)
+            fields = sorted(fe)
+            sens = np.stack([fe[f] for f in fields], axis=-1)
+            worst = {f: float(np.nanmax(fe[f])) for f in fields}
+            assert 4.0 * np.nanmax(sens) <= 1e-6, f"{name} amp{amp}: the reference itself is ill-conditioned here: {worst}"
+            tag = f"{name}_amp{amp}"
+            out[f"{tag}_rec"] = rec; out[f"{tag}_steps"] = np.int64(steps)
+            out[f"{tag}_sens"] = sens.astype(np.float32); out[f"{tag}_sens_fields"] = np.array(fields)
+            lat = rec[..., H.REC["STATE"] + 1][rec[..., H.REC["VALID"]] > 0]
+            print(f"{tag}: {steps} steps, {int((rec[..., H.REC['VALID']] > 0).sum())} of {rec.shape[0] * rec.shape[1]} legs VALID, arrival latitudes "
+                  f"{np.degrees(lat.min()):.2f} .. {np.degrees(lat.max()):.2f} deg; worst sensitivity " + ", ".join(f"{f} {v:.1e}" for f, v in worst.items()))
+    path = os.path.join(OUT, "global_polar.npz")
+    np.savez_compressed(path, **out)
+    print("polar ->", path, os.path.getsize(path) // 1024, "KiB")
+
+
+# ---- range-dependent spherical set at high latitude (tests/test_gpu_globalrd.py, test_gpu_probes.py, test_oracle_globalrd.py) ----
+# rngdep_data.POLAR_GRID: the committed columns on rows 82 .. 89.5 N, 15 degrees of longitude apart (116 km at the source, 14.6 km on the last row).  5 x 7 fan
+# from 86 N: towards the pole and 3, 8 degrees beside it (arrivals at 88.9 .. 89.35 N, the steeper rays; the shallow ones leave over the last row), sideways
+# (leaves through the longitude box or arrives at 84 N) and away.  Every second leg leaves the grid: BROKE, with an exact step count, is part of what is pinned.
+RDPOLAR_SRC = (0.0, 86.0, 0.0)
+RDPOLAR_TH = [3.0, 20.0, 24.0, 28.0, 33.0]
+RDPOLAR_AZ = [-3.0, 0.0, 3.0, 8.0, 110.0, 180.0, -160.0]
+
+
+def main_globalrd_polar():
+    """globalrd_polar.npz: Global.RngDep on the polar grid, compiled reference libref_globalrd.so (a process of its own: the reference holds one grid), the
+    oracle asserted equal bit for bit.  Records of the fan (bounces = 1, amplitudes on), the reference's own answer to theta (1 + 1e-12) per arrival and
+    field (4 x that <= 1e-6 asserted: no exemptions), and Eval_Spline_AllOrder2 / the scalar API at 400 points of the grid."""
+    import tempfile
+    import rngdep_data as RD
+    from parity import field_errors
+    eq = H.EQ_GLOBAL_RNGDEP
+    grid = RD.write_grid_global(os.path.join(tempfile.gettempdir(), "ggp"), **RD.POLAR_GRID)
+    R = H.RefShim(eq, grid=grid)
+    O = H.Oracle(eq, met=None); O.load_grid(*grid)
+    lat_n, lon_n = RD.lat_nodes_global(RD.POLAR_GRID["centre_lat"], RD.POLAR_GRID["lat_step"]), RD.lon_nodes_global(RD.POLAR_GRID["lon_step"])
+    out = {"lat_nodes": lat_n, "lon_nodes": lon_n, "src": np.array(RDPOLAR_SRC)}
+    rng = np.random.default_rng(2026)
+    n = 400
+    # a third of a cell beyond the rows and columns, as the mid-latitude probes; below the pole
+    r = 6370.0 + rng.uniform(-1, 141, n); lat = np.radians(rng.uniform(81.4, 89.95, n)); lon = np.radians(rng.uniform(-35, 35, n))
+    r[:6] = 6370.0 + np.array([0, 139.6, 10, 0.4, 70, 0.0]); lat[:6] = np.radians([lat_n[0], lat_n[4], lat_n[2], lat_n[1], lat_n[3], 84.8]); lon[:6] = np.radians([lon_n[0], lon_n[4], 0, lon_n[3], lon_n[1], 0])
+    o30, a8 = R.grid_probe(r, lat, lon)
+    oo30, oa8 = O.grid_probe(r, lat, lon)
+    assert np.array_equal(oo30, o30) and np.array_equal(oa8, a8), "the oracle's interpolant differs from the compiled reference's"
+    out.update(probe_r=r, probe_lat=lat, probe_lon=lon, probe_out30=o30, probe_api8=a8)
+    th = np.array([t for a in RDPOLAR_AZ for t in RDPOLAR_TH]); ph = np.array([a for a in RDPOLAR_AZ for t in RDPOLAR_TH])
+    out.update(theta=th, phi=ph)
+    cfg = H.make_cfg(eq, bounces=1, calc_amp=True, mode=0, src=RDPOLAR_SRC)
+    steps, rec, _, _ = R.fan(cfg, th, ph)
+    so, ro, _, _ = O.fan(cfg, th, ph)
+    assert so == steps and np.array_equal(ro, rec), "the oracle's records differ from the compiled reference's"
+    sp, rp, _, _ = R.fan(cfg, th * (1.0 + POLAR_SENS_EPS), ph)
+    for f in ("VALID", "STEPS", "BROKE"):
+        assert np.array_equal(rp[..., H.REC[f]], rec[..., H.REC[f]]), f"{f} moves with theta (1 + {POLAR_SENS_EPS:g})"
+    fe = field_errors(rp, rec, 18, 0)
+    fields = sorted(fe)
+    sens = np.stack([fe[f] for f in fields], axis=-1)
+    worst = {f: float(np.nanmax(fe[f])) for f in fields}
+    assert 4.0 * np.nanmax(sens) <= 1e-6, f"the reference itself is ill-conditioned here: {worst}"
+    out.update(rec_amp1=rec, steps_amp1=np.int64(steps), sens=sens.astype(np.float32), sens_fields=np.array(fields), sens_eps=np.float64(POLAR_SENS_EPS))
+    valid = rec[..., H.REC["VALID"]] > 0
+    lat_a = np.degrees(rec[..., H.REC["STATE"] + 1][valid])
+    print(f"globalrd_polar: {steps} steps, {int(valid.sum())} arrivals at {lat_a.min():.2f} .. {lat_a.max():.2f} N, {int((rec[..., H.REC['BROKE']] > 0).sum())} legs BROKE; worst sensitivity "
+          + ", ".join(f"{f} {v:.1e}" for f, v in worst.items()))
+    path = os.path.join(OUT, "globalrd_polar.npz")
+    np.savez_compressed(path, **out)
+    print("globalrd_polar ->", path, os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "globalrd":
+    if len(sys.argv) > 1 and sys.argv[1] == "polar":
+        main_polar()
+    elif len(sys.argv) > 1 and sys.argv[1] == "globalrd_polar":
+        main_globalrd_polar()
+    elif len(sys.argv) > 1 and sys.argv[1] == "globalrd":
         main_globalrd()
     elif len(sys.argv) > 1 and sys.argv[1] == "rngdep":
         main_rngdep()

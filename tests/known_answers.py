@@ -129,3 +129,16 @@ def hamiltonian_residuals(eq, rec, atmo9_at, c_src):
         res = (nu * mu).sum(axis=1) / mag + mag / c * dc * Rz + ((mu * wind).sum(axis=1) + (nu * dwind).sum(axis=1) * Rz) / c
         worst_d = max(worst_d, float((np.abs(res) / np.maximum(np.linalg.norm(mu, axis=1), 1e-30)).max()))
     return int(valid.sum()), float(np.abs(H).max()), worst_d
+
+
+def polar_fan_with_crossing(name="n89"):
+    """source and launch angles of a polar fan of tests/golden/global_polar.npz (make_golden.py `polar`) plus the rays the fixture had to leave out: the ones
+    aimed AT the pole, one per inclination (lat passes pi/2 and cos(lat) changes sign on them; the reference's own records of those are not conditioned well
+    enough for a 1e-6 comparison, so they appear only in checks that need no reference).  Returns (src, theta, phi, number of fixture rays)."""
+    import os
+    from harness import GOLDEN_DIR
+    g = np.load(os.path.join(GOLDEN_DIR, "global_polar.npz"))
+    th, ph = g[f"{name}_theta"], g[f"{name}_phi"]
+    inc = np.unique(th)
+    poleward = 0.0 if g[f"{name}_src"][1] > 0 else 180.0
+    return tuple(g[f"{name}_src"]), np.concatenate([th, inc]), np.concatenate([ph, np.full_like(inc, poleward)]), len(th)

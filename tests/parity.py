@@ -151,6 +151,37 @@ def max_rel_errors(got, want, E, hidx="auto"):
     return out
 
 
+def field_errors(got, want, E, hidx="auto"):
+    """diagnostic: the error of every (ray, leg) in every field compare_records judges, by compare_records' own measures (floors, degrees
+    against 180, the end state against its column scale over the fan: the worst component) - dict field -> [n_rays][legs], NaN where the
+    field is not judged.  No asserts; got and want must have the same counts for the figures to mean anything."""
+    if hidx == "auto":
+        hidx = HEIGHT_COMP.get(E)
+    ran = want[..., REC["STEPS"]] > 0
+    valid = want[..., REC["VALID"]] > 0
+    out = {}
+
+    def put(f, m, e):
+        a = np.full(want.shape[:2], np.nan)
+        a[m] = e
+        out[f] = a
+    for f, floor in (("TTIME", 1e-3), ("ATTEN", 1e-12)):
+        put(f, ran, _rel(got[..., REC[f]][ran], want[..., REC[f]][ran], floor))
+    for f in ("TURN", "RANGE"):
+        put(f, valid, _rel(got[..., REC[f]][valid], want[..., REC[f]][valid], 1e-3))
+    for f in ("INCL", "BACKAZ"):
+        put(f, valid, np.abs(got[..., REC[f]][valid] - want[..., REC[f]][valid]) / 180.0)
+    st_g = got[..., REC["STATE"]:REC["STATE"] + E][valid]
+    st_w = want[..., REC["STATE"]:REC["STATE"] + E][valid]
+    if st_w.size:
+        scale = _state_scale(st_w, want, valid, hidx)
+        put("STATE", valid, (np.abs(st_g - st_w) / np.maximum(np.abs(st_w), _state_floor(E, hidx) * scale)).max(axis=1))
+    if E > 6:
+        for f in ("AMP", "JACOB"):
+            put(f, valid, _rel(got[..., REC[f]][valid], want[..., REC[f]][valid], 1e-300))
+    return out
+
+
 def fan_properties(rec, steps, E, nu_slice, c_ratio, eik_tol=1e-4):
     """size-independent properties of a fan's record table (no reference needed): count bookkeeping - the legs' step counts add up to the
     device counter, a leg that broke has no later legs, legs run in order, a row is written exactly for the legs that ran and did not

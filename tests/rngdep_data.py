@@ -75,6 +75,19 @@ def write_grid(dirpath, short_paths=True, thin=THIN):
 LAT_NODES = np.array([25.0, 28.0, 31.0, 34.0, 37.0])
 LON_NODES = np.array([-8.0, -4.0, 0.0, 4.0, 8.0])
 GRID_GLOBAL_NPZ = os.path.join(H.GOLDEN_DIR, "globalrd_grid.npz")
+# the same columns around another centre latitude: the perturbation depends on a node's INDEX offset from the centre ((lat - 31) / 6 = -1 .. 1 above), so a grid
+# whose rows are `lat_step` apart around `centre_lat` holds the committed columns and differs in loc_lat.dat alone.  POLAR_GRID: 82 .. 89.5 N, where the
+# 4-degree longitude cells shrink from 62 km to 3.9 km (tests/golden/globalrd_polar.npz, tests/test_gpu_globalrd.py)
+CENTRE_LAT, LAT_STEP, LON_STEP = 31.0, 3.0, 4.0
+POLAR_GRID = dict(centre_lat=85.75, lat_step=1.875, lon_step=15.0)
+
+
+def lat_nodes_global(centre_lat=CENTRE_LAT, lat_step=LAT_STEP):
+    return centre_lat + lat_step * np.arange(-2.0, 3.0)
+
+
+def lon_nodes_global(lon_step=LON_STEP):
+    return lon_step * np.arange(-2.0, 3.0)
 
 
 def grid_columns_global():
@@ -98,8 +111,13 @@ def save_grid_global_npz():
     np.savez_compressed(GRID_GLOBAL_NPZ, z=z, T=T, u=u, v=v, rho=rho, p=p, lat=LAT_NODES, lon=LON_NODES)
 
 
-def write_grid_global(dirpath, short_paths=True):
-    """writes g<n>.met, loc_lat.dat, loc_lon.dat; returns (prefix, loclat, loclon)"""
+def write_grid_global(dirpath, short_paths=True, centre_lat=CENTRE_LAT, lat_step=LAT_STEP, lon_step=LON_STEP):
+    """writes g<n>.met, loc_lat.dat, loc_lon.dat; returns (prefix, loclat, loclon).  centre_lat, lat_step: the latitudes of the five rows (the default:
+    LAT_NODES, the files the fixtures of the mid-latitude grid were made from)"""
+    lat_nodes = lat_nodes_global(centre_lat, lat_step)
+    lon_nodes = lon_nodes_global(lon_step)
+    assert (centre_lat, lat_step, lon_step) != (CENTRE_LAT, LAT_STEP, LON_STEP) or (np.array_equal(lat_nodes, LAT_NODES) and np.array_equal(lon_nodes, LON_NODES))
+    assert np.abs(lat_nodes).max() < 90.0
     os.makedirs(dirpath, exist_ok=True)
     g = np.load(GRID_GLOBAL_NPZ)
     z, T, u, v, rho, p = g["z"], g["T"], g["u"], g["v"], g["rho"], g["p"]
@@ -113,7 +131,7 @@ def write_grid_global(dirpath, short_paths=True):
                     fh.write(f"{z[k]:.10g} {T[i, j, k]:.12g} {u[i, j, k]:.12g} {v[i, j, k]:.12g} {rho[i, j, k]:.12g} {p[k]:.10g}\n")
     loclat, loclon = os.path.join(dirpath, "loc_lat.dat"), os.path.join(dirpath, "loc_lon.dat")
     with open(loclat, "w") as fh:
-        fh.write("".join(f"{x:.10g}\n" for x in LAT_NODES))
+        fh.write("".join(f"{x:.10g}\n" for x in lat_nodes))
     with open(loclon, "w") as fh:
-        fh.write("".join(f"{y:.10g}\n" for y in LON_NODES))
+        fh.write("".join(f"{y:.10g}\n" for y in lon_nodes))
     return prefix, loclat, loclon

@@ -1,12 +1,14 @@
 """GPU parity of the range-dependent spherical set (GeoAcGlobal.RngDep) against golden vectors from the compiled reference:
 synthetic 5x5 lat/lon grid of perturbed profiles, 3 x 4 degree cells (tests/rngdep_data.py)."""
+import faulthandler
+
 import numpy as np
 import pytest
 
 import harness as H
 from geoac_amd.api import DEFAULT_OPTIONS as OPT      # launch-plan options of the contexts the tests create (geoac_set_option)
 import rngdep_data as RD
-from parity import compare_records, max_rel_errors
+from parity import compare_records, field_errors, max_rel_errors
 
 pytestmark = pytest.mark.gpu
 EQ = H.EQ_GLOBAL_RNGDEP
@@ -150,3 +152,59 @@ def test_leg_records_do_not_depend_on_the_number_of_bounces(grid, amp):
     for a in (0, 1):
         for b in range(a + 1, 3):
             assert np.array_equal(recs[b][:, :a + 1].view(np.uint64), recs[a].view(np.uint64)), (a, b)
+
+
+# ---- the same set at high latitude: rows at 82 .. 89.5 N, 15 degrees of longitude apart (116 km at the source, 14.6 km on the last row); fixture
+#      tests/golden/globalrd_polar.npz from the compiled reference (make_golden.py globalrd_polar) ----
+STEP_LIMIT_S = 120
+
+
+@pytest.fixture
+def time_limit():
+    faulthandler.dump_traceback_later(STEP_LIMIT_S, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+@pytest.fixture(scope="module")
+def gold_polar():
+    return np.load(f"{H.GOLDEN_DIR}/globalrd_polar.npz")
+
+
+@pytest.fixture(scope="module")
+def grid_polar(tmp_path_factory):
+    return RD.write_grid_global(str(tmp_path_factory.mktemp("ggp")), short_paths=False, **RD.POLAR_GRID)
+
+
+def test_globalrd_polar_fan_vs_golden(gold_polar, grid_polar, time_limit):
+    """5 x 7 fan from 86 N, towards the pole and beside it, sideways and away, one bounce, amplitudes on: VALID / STEPS / BROKE of every leg and the
+    step total exact, every field compare_records judges within 1e-6.  The reference's own conditioning (theta (1 + 1e-12), in the fixture) covers every
+    field of every arrival: no exemptions."""
+    g = gold_polar
+    assert 4.0 * np.nanmax(g["sens"]) <= 1e-6
+    want = g["rec_amp1"]
+    valid = want[..., H.REC["VALID"]] > 0
+    assert valid.sum() >= 10 and np.degrees(want[..., H.REC["STATE"] + 1][valid]).max() > 89.0 and (want[..., H.REC["BROKE"]] > 0).sum() > 0
+    ctx = _ctx(grid_polar, bounces=1, calc_amp=1, mode=0, src=tuple(g["src"]))
+    rec, steps = ctx.run(g["theta"], g["phi"])
+    fe = field_errors(rec, want, 18, 0)
+    print("globalrd polar: worst error per field: " + ", ".join(f"{f} {np.nanmax(fe[f]):.2e}" for f in sorted(fe)))
+    assert steps == int(g["steps_amp1"])
+    compare_records(rec, want, E=18, hidx=0)
+
+
+@pytest.mark.parametrize("lanes", [1, 4, "coop", "dense"])
+def test_globalrd_polar_lanes_per_ray_variants_vs_golden(gold_polar, grid_polar, lanes, monkeypatch, time_limit):
+    """the launches of test_every_lanes_per_ray_variant_vs_golden that every build holds, on the polar grid: the wave-cooperative gather ("coop") and its
+    per-lane twin ("dense") as a large fan runs them, one and four lanes per ray"""
+    g = gold_polar
+    if lanes in ("coop", "dense"):
+        monkeypatch.setitem(OPT, "GRID_LANES", "1")
+        monkeypatch.setitem(OPT, "SPREAD", "1")
+        monkeypatch.setitem(OPT, "GRID_COOP", "1" if lanes == "coop" else "0")
+    else:
+        monkeypatch.setitem(OPT, "GRID_LANES", str(lanes))
+    ctx = _ctx(grid_polar, bounces=1, calc_amp=1, mode=0, src=tuple(g["src"]))
+    rec, steps = ctx.run(g["theta"], g["phi"])
+    assert steps == int(g["steps_amp1"])
+    compare_records(rec, g["rec_amp1"], E=18, hidx=0)

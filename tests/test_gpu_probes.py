@@ -81,16 +81,13 @@ def test_cartesian_grid_interpolant_vs_reference(coop, tmp_path):
     assert e.max() <= RTOL and ea.max() <= RTOL
 
 
-@pytest.mark.parametrize("coop", [False, True])
-def test_spherical_grid_interpolant_vs_reference(coop, tmp_path):
-    """the spherical twin with its quirks Q12: G2S_GlobalMultiDimSpline3D.cpp:1224-1461, 1502-1611.  The reference orders its outputs
-    f, r, t, p, rr, tt, pp, rt, rp, tp; the device table order is (lat, lon, r)"""
+def _spherical_grid_interpolant_vs_reference(coop, tmp_path, fixture, grid_kw, src, tag):
     import geoac_amd as G
     import rngdep_data as RD
-    g = np.load(f"{H.GOLDEN_DIR}/globalrd_small.npz")
+    g = np.load(f"{H.GOLDEN_DIR}/{fixture}")
     ctx = G.FanContext(G.EQ_GLOBAL_RNGDEP, device=0)
-    ctx.load_grid(*RD.write_grid_global(str(tmp_path), short_paths=False))
-    ctx.set_params(bounces=0, calc_amp=1, mode=0, src=(0.0, 31.0, 0.0))
+    ctx.load_grid(*RD.write_grid_global(str(tmp_path), short_paths=False, **grid_kw))
+    ctx.set_params(bounces=0, calc_amp=1, mode=0, src=src)
     ctx.run(np.array([20.0]), np.array([-90.0]))
     o30, a7 = ctx.probe_grid(g["probe_lat"], g["probe_lon"], g["probe_r"], coop=coop)
     dev_of_ref = [0, 3, 1, 2, 6, 4, 5, 8, 9, 7]                  # reference slot q <- device slot
@@ -104,9 +101,49 @@ def test_spherical_grid_interpolant_vs_reference(coop, tmp_path):
     e_nodes = _colwise(got[:6][:, ~second], want[:6][:, ~second], field_scale=_field_scales(want)[~second])
     e = np.concatenate([e, e_nodes])
     ea = _colwise(a7, g["probe_api8"][:, :7])
-    print("globalrd coop" if coop else "globalrd", "AllOrder2 max rel err", f"{e.max():.1e}", "scalar API", [f"{v:.1e}" for v in ea])
+    print(tag + " coop" if coop else tag, "AllOrder2 max rel err", f"{e.max():.1e}", "scalar API", [f"{v:.1e}" for v in ea])
     print("   per column", [f"{v:.0e}" for v in e])
     assert e.max() <= RTOL and ea.max() <= RTOL
+
+
+@pytest.mark.parametrize("coop", [False, True])
+def test_spherical_grid_interpolant_vs_reference(coop, tmp_path):
+    """the spherical twin with its quirks Q12: G2S_GlobalMultiDimSpline3D.cpp:1224-1461, 1502-1611.  The reference orders its outputs
+    f, r, t, p, rr, tt, pp, rt, rp, tp; the device table order is (lat, lon, r)"""
+    _spherical_grid_interpolant_vs_reference(coop, tmp_path, "globalrd_small.npz", {}, (0.0, 31.0, 0.0), "globalrd")
+
+
+@pytest.fixture
+def time_limit():
+    import faulthandler
+    faulthandler.dump_traceback_later(120, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+@pytest.mark.parametrize("coop", [False, True])
+def test_polar_grid_interpolant_vs_reference(coop, tmp_path, time_limit):
+    """the same 30 values and scalar API at 400 points of the grid whose rows lie at 82 .. 89.5 N (rngdep_data.POLAR_GRID; reference values in
+    tests/golden/globalrd_polar.npz): points up to 89.95 N, beyond the last row, and beyond the first and last column"""
+    import rngdep_data as RD
+    _spherical_grid_interpolant_vs_reference(coop, tmp_path, "globalrd_polar.npz", RD.POLAR_GRID, (0.0, 86.0, 0.0), "globalrd polar")
+
+
+def test_cooperative_and_per_lane_gathers_give_the_same_bits_on_the_polar_grid(tmp_path, time_limit):
+    """the twin of the test below on the polar grid: 4096 random points between its first and last rows and columns"""
+    import geoac_amd as G
+    import rngdep_data as RD
+    rng = np.random.default_rng(6)
+    n = 4096
+    ctx = G.FanContext(G.EQ_GLOBAL_RNGDEP, device=0)
+    ctx.load_grid(*RD.write_grid_global(str(tmp_path), short_paths=False, **RD.POLAR_GRID))
+    ctx.set_params(bounces=0, calc_amp=1, mode=0, src=(0.0, 86.0, 0.0))
+    ctx.run(np.array([20.0]), np.array([-90.0]))
+    a = (np.radians(rng.uniform(82.1, 89.45, n)), np.radians(rng.uniform(-29.0, 29.0, n)), 6370.0 + rng.uniform(0.0, 130.0, n))
+    o0, a0 = ctx.probe_grid(*a, coop=False)
+    o1, a1 = ctx.probe_grid(*a, coop=True)
+    assert np.isfinite(o0).all()
+    assert np.array_equal(o0, o1) and np.array_equal(a0, a1)
 
 
 @pytest.mark.parametrize("eqname", ["EQ_3D_RNGDEP", "EQ_GLOBAL_RNGDEP"])

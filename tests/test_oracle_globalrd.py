@@ -51,3 +51,23 @@ def test_alt_config_bitexact(gold):
     steps, rec, _, _ = O.fan(cfg, gold["theta"], gold["phi"])
     assert steps == int(gold["steps_alt"])
     assert np.array_equal(rec, gold["rec_alt"])
+
+
+def test_polar_grid_bitexact(tmp_path):
+    """the grid whose rows lie at 82 .. 89.5 N (rngdep_data.POLAR_GRID; make_golden.py globalrd_polar): interpolant and fan records of the compiled reference"""
+    g = np.load(f"{H.GOLDEN_DIR}/globalrd_polar.npz")
+    O = H.Oracle(EQ, met=None)
+    O.load_grid(*RD.write_grid_global(str(tmp_path), short_paths=False, **RD.POLAR_GRID))
+    o30, a8 = O.grid_probe(g["probe_r"], g["probe_lat"], g["probe_lon"])
+    assert np.array_equal(o30, g["probe_out30"]) and np.array_equal(a8, g["probe_api8"])
+    cfg = H.make_cfg(EQ, bounces=1, calc_amp=True, mode=0, src=tuple(g["src"]))
+    rows = np.array([2, 9, 18, 25, 31])          # a ray per direction (the fixture script ran the oracle on all 35): arrivals at 89.3 N and 82.1 N, short tropospheric legs
+    steps, rec, _, _ = O.fan(cfg, g["theta"][rows], g["phi"][rows])
+    assert steps == int(g["rec_amp1"][rows][..., H.REC["STEPS"]].sum())
+    assert np.array_equal(rec, g["rec_amp1"][rows])
+
+
+def test_default_grid_files_are_unchanged(tmp_path):
+    """write_grid_global without a centre latitude writes the node files the mid-latitude fixtures were made from"""
+    _, loclat, loclon = RD.write_grid_global(str(tmp_path), short_paths=False)
+    assert open(loclat).read() == "25\n28\n31\n34\n37\n" and open(loclon).read() == "-8\n-4\n0\n4\n8\n"
