@@ -10,5 +10,6 @@ from .api import (  # noqa: F401
     met_load, natural_spline_slopes, fan_enumerate, default_params, options, option_names, has_ab_kernels, build_id, DEFAULT_OPTIONS,
     MapSpec, map_spec, map_check, MAP_COUNT, MAP_TTIME_MIN, MAP_CEL_MAX, MAP_LEVEL_MAX, MAP_BEST,
     StationSpec, station_spec, station_check, STA, STA_STRIDE,
+    RefineSpec, refine_spec, refine_check, RFN, RFN_STRIDE, RFN_STATUS, RFN_MAX_RAY_MEMBERS,
     TubeSpec, tube_spec, tube_check, TUBE, TUBE_MAX_SPAN, TUBE_COOP_MIN,
 )

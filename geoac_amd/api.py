@@ -83,6 +83,32 @@ def station_check(eqset, spec, n_rays, n_sta):
         raise GeoAcError(f"geoac_station_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
 
 
+class RefineSpec(ctypes.Structure):
+    """geoac_refine_spec (include/geoac_refine.h): round limit, shrink limit, tolerance [km] and step cut [deg] of a station refinement"""
+    _fields_ = [("max_iter", ctypes.c_int), ("max_shrink", ctypes.c_int), ("tol", ctypes.c_double), ("step_max_deg", ctypes.c_double)]
+
+
+RFN_STRIDE = 16
+RFN = dict(MEMBER=0, STATION=1, LEG=2, TRI=3, STATUS=4, ITER=5, THETA=6, PHI=7, MISS=8, TTIME=9, CELERITY=10, TURN=11, INCL=12, BACKAZ=13, AMP=14, JACOB=15)
+RFN_STATUS = dict(CONVERGED=1, ITER_LIMIT=2, STALLED=3, LOST=4, SINGULAR=5)
+RFN_MAX_RAY_MEMBERS = 1 << 20
+
+
+def refine_spec(max_iter=8, max_shrink=4, tol=0.1, step_max_deg=0.2):
+    """a RefineSpec from plain values"""
+    return RefineSpec(int(max_iter), int(max_shrink), float(tol), float(step_max_deg))
+
+
+def refine_check(eqset, spec):
+    """geoac_refine_check: host-only validation (no GPU needed); raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_refine_fault.restype = ctypes.c_char_p
+    rc = lib.geoac_refine_check(int(eqset), ctypes.byref(spec))
+    if rc:
+        fault = lib.geoac_refine_fault(int(eqset), ctypes.byref(spec))
+        raise GeoAcError(f"geoac_refine_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
+
+
 class TubeSpec(ctypes.Structure):
     """geoac_tube_spec (include/geoac_tubemap.h): the grid of a MapSpec, the lattice and triangle filters of a StationSpec, the band on a hit's
     interpolated turning height and the detection threshold of a tube map"""
@@ -499,6 +525,31 @@ class FanContext:
         ms = ctypes.c_double(0)
         self._chk(self.lib.geoac_fan_stations_timing(self._h, ctypes.byref(ms)))
         return ms.value
+
+    # ---- station refinement (include/geoac_refine.h): rounds, step rule and rows run on the device; nothing is computed here ----
+    def refine(self, spec=None, **kw):
+        """geoac_fan_refine of the current station lists (stations() after a calc_amp = 1 lattice launch): `spec` a RefineSpec, or the arguments of
+        refine_spec().  Returns rows [n_seeds][RFN_STRIDE] (columns RFN, status values RFN_STATUS), level [n_seeds][F] and a dict of counters.  The
+        call replaces the context's launch angles and last launch by its own last round (n_rays becomes n_seeds when there are any)."""
+        if spec is None:
+            spec = refine_spec(**kw)
+        self._chk(self.lib.geoac_fan_refine(self._h, ctypes.byref(spec)))
+        n, F, it = (ctypes.c_int(0) for _ in range(3))
+        self._chk(self.lib.geoac_fan_refine_shape(self._h, *[ctypes.byref(v) for v in (n, F, it)]))
+        n, F = n.value, F.value
+        rows, level = np.empty((n, RFN_STRIDE)), np.empty((n, F))
+        self._chk(self.lib.geoac_fan_refine_fetch(self._h, _p(rows), _p(level)))
+        st = np.zeros(6, dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_refine_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
+        if n:
+            self.n_rays = n
+        return rows, level, dict(zip(("launches", "ray_members", "seeds", "converged", "stalled_or_limit", "lost_or_singular"), (int(v) for v in st)))
+
+    def refine_timing(self):
+        """HIP-event times of the last refine() [ms]: its launches, its own kernels"""
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        self._chk(self.lib.geoac_fan_refine_timing(self._h, ms))
+        return dict(launch_ms=ms[0], kernel_ms=ms[1])
 
     # ---- tube maps (include/geoac_tubemap.h): the rasteriser runs on the device; nothing is computed here ----
     def tubemap(self, spec=None, **kw):

@@ -24,6 +24,7 @@
 #include "geoac_map_int.h"
 #include "geoac_stations_int.h"
 #include "geoac_tubemap_int.h"
+#include "geoac_refine_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s);
@@ -233,6 +234,9 @@ struct geoac_ctx {
     void* map_state = nullptr;
     void* sta_state = nullptr;                    // station arrivals (geoac_stations.hip): NULL until the first geoac_fan_stations
     void* tube_state = nullptr;                   // tube maps (geoac_tubemap.hip): NULL until the first geoac_fan_tubemap
+    void* rfn_state = nullptr;                    // station refinement (geoac_refine.hip): NULL until the first geoac_fan_refine
+    std::vector<double> rfn_mem;                  // [M][GEOAC_RFN_MEMW] of the last geoac_rfn_view
+    std::vector<double> ens_u, ens_v;             // every member's winds on the host (K > 1), beside ens_T: the Mach numbers at the source the refinement needs
     std::string err;
 };
 
@@ -426,6 +430,7 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->map_state){ geoac_map_release(ctx->map_state); ctx->map_state = nullptr; }
     if(ctx->sta_state){ geoac_sta_release(ctx->sta_state); ctx->sta_state = nullptr; }
     if(ctx->tube_state){ geoac_tube_release(ctx->tube_state); ctx->tube_state = nullptr; }
+    if(ctx->rfn_state){ geoac_rfn_release(ctx->rfn_state); ctx->rfn_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->nrows[0], &ctx->nrows[1], &ctx->nrows[2], &ctx->legend[0], &ctx->legend[1], &ctx->legend[2],
@@ -530,8 +535,9 @@ static int upload_members(geoac_ctx* ctx, int K, int n, const double* x, const d
     ctx->ran = false;                             // (the probes launch with the tables of the last fan: not after a new upload)
     const int K_was = ctx->n_members;
     ctx->n_members = K;
-    if(K > 1){ ctx->ens_T.assign(T, T + K * nn); ctx->ens_rho.assign(rho, rho + K * nn); ctx->ens_sl.assign(slopes4, slopes4 + 4 * nn * K); }
-    else { ctx->ens_T.clear(); ctx->ens_rho.clear(); ctx->ens_sl.clear(); }
+    if(K > 1){ ctx->ens_T.assign(T, T + K * nn); ctx->ens_rho.assign(rho, rho + K * nn); ctx->ens_sl.assign(slopes4, slopes4 + 4 * nn * K);
+               ctx->ens_u.assign(u, u + K * nn); ctx->ens_v.assign(v, v + K * nn); }
+    else { ctx->ens_T.clear(); ctx->ens_rho.clear(); ctx->ens_sl.clear(); ctx->ens_u.clear(); ctx->ens_v.clear(); }
     if(K != K_was && ctx->have_angles) return layout_angles(ctx);       // (the slot layout depends on K, and on the sources)
     return GEOAC_OK;
 }
@@ -1606,6 +1612,42 @@ int geoac_tube_view(geoac_ctx* ctx, GeoacTubeView* v){
     if(rc) return rc;
     v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
     v->state = &ctx->tube_state;
+    return GEOAC_OK;
+}
+
+// ... and geoac_refine.hip (geoac_refine_int.h): the same view, the members' source points and (GEOAC_EQ_3D) wind Mach numbers at the source, evaluated
+// on the host as geoac_medium_1d evaluates them for a single profile
+int geoac_rfn_view(geoac_ctx* ctx, GeoacRfnView* v){
+    int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
+    if(rc) return rc;
+    const int K = ctx->n_members, M = ctx->n_src * K;
+    const bool sph = (ctx->eqset == GEOAC_EQ_GLOBAL || ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP);
+    ctx->rfn_mem.assign((size_t)M * GEOAC_RFN_MEMW, 0.0);
+    const size_t n = (size_t)ctx->n_nodes;
+    for(int m = 0; m < M; m++){
+        const double* src = ctx->n_src > 1 ? &ctx->sources[(size_t)(m / K) * 3] : ctx->prm.src;
+        double* o = &ctx->rfn_mem[(size_t)m * GEOAC_RFN_MEMW];
+        o[0] = sph ? src[1] : src[0]; o[1] = sph ? src[2] : src[1];
+        if(ctx->eqset == GEOAC_EQ_3D && ctx->have_atmo && !ctx->have_grid){
+            const double z = std::max(src[2], ctx->prm.z_grnd);
+            const int k = m % K;
+            double c, u, w;
+            if(K > 1){
+                const std::vector<double> Tk(ctx->ens_T.begin() + k * n, ctx->ens_T.begin() + (k + 1) * n), uk(ctx->ens_u.begin() + k * n, ctx->ens_u.begin() + (k + 1) * n),
+                                          vk(ctx->ens_v.begin() + k * n, ctx->ens_v.begin() + (k + 1) * n);
+                const double* sl = ctx->ens_sl.data() + 4 * n * k;
+                c = sqrt(kGamR * host_spline_f(ctx->x, Tk, sl, z)); u = host_spline_f(ctx->x, uk, sl + n, z); w = host_spline_f(ctx->x, vk, sl + 2 * n, z);
+            } else {
+                c = sqrt(kGamR * host_spline_f(ctx->x, ctx->T, ctx->sl.data(), z)); u = host_spline_f(ctx->x, ctx->u, ctx->sl.data() + n, z);
+                w = host_spline_f(ctx->x, ctx->v, ctx->sl.data() + 2 * n, z);
+            }
+            o[2] = u / c; o[3] = w / c;
+        }
+    }
+    v->n_members = M; v->mem = ctx->rfn_mem.data();
+    v->r_earth = ctx->prm.r_earth; v->z_grnd = ctx->prm.z_grnd;
+    v->calc_amp = ctx->prm.calc_amp ? 1 : 0; v->mode = ctx->prm.mode;
+    v->state = &ctx->rfn_state;
     return GEOAC_OK;
 }
 

@@ -426,6 +426,16 @@ extern "C" int geoac_fan_stations_shape(geoac_ctx* ctx, int* n_members, int* n_f
     return GEOAC_OK;
 }
 
+// for geoac_refine.hip (geoac_refine_int.h): the stations of the current lists as the kernels read them (the tail of `axes`)
+extern "C" int geoac_sta_coords_dev(geoac_ctx* ctx, const double** sta_dev, int* n_sta){
+    Bound b;
+    int rc = bind_lists(ctx, "fan_refine", &b);
+    if(rc) return rc;
+    if(sta_dev) *sta_dev = (const double*)b.st->axes + (b.st->h_axes.size() - 2 * (size_t)b.st->n_sta);
+    if(n_sta) *n_sta = b.st->n_sta;
+    return GEOAC_OK;
+}
+
 extern "C" int geoac_fan_stations_dev(geoac_ctx* ctx, int which, void** dev_ptr, size_t* bytes){
     Bound b;
     int rc = bind_lists(ctx, "fan_stations_dev", &b);

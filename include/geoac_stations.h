@@ -4,7 +4,7 @@
  * maps every lattice triangle to a landing triangle per leg.  A landing triangle that encloses a station contains an eigenray to first order,
  * and barycentric interpolation inside it gives that eigenray's launch angles, travel time, celerity, turning height, arrival angles and level.
  * This is the classical first stage of an eigenray search (the reference's GeoAc_EstimateEigenray does it one scan at a time); the estimates
- * are the natural seeds of a refinement (-eig_direct).  Nothing is refined here.
+ * are the natural seeds of a refinement (-eig_direct; geoac_fan_refine, geoac_refine.h).  Nothing is refined here.
  *
  * geoac_fan_stations reads only the record table, the launch angles and the level table (geoac_map.h), so it serves the four 3-D equation
  * sets alike and every member of an ensemble, a source set or a frequency set: M = n_src * K members, F = n_freq, as in geoac_map.h.
