@@ -481,19 +481,25 @@ class FanContext:
         if spec is None:
             spec = map_spec(**kw)
         self._chk(self.lib.geoac_fan_map(self._h, ctypes.byref(spec)))
+        out = self._fetch_layers("geoac_fan_map", _MAP_LAYERS, MAP_LEVEL_MAX, spec)
+        out["outside"] = np.empty(out["count"].shape[0], dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_map_outside(self._h, out["outside"].ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def _fetch_layers(self, fn, layers, first_mf, spec):
+        """the layers of the current map made by `fn` (geoac_fan_map / geoac_fan_tubemap: <fn>_shape, <fn>_fetch, <fn>_fetch_detect) as a dict of
+        numpy arrays; the layers from `first_mf` on are per frequency; detect when the spec has a detect_db"""
         M, F, n0, n1 = (ctypes.c_int(0) for _ in range(4))
-        self._chk(self.lib.geoac_fan_map_shape(self._h, *[ctypes.byref(v) for v in (M, F, n0, n1)]))
+        self._chk(getattr(self.lib, fn + "_shape")(self._h, *[ctypes.byref(v) for v in (M, F, n0, n1)]))
         M, F, n0, n1 = M.value, F.value, n0.value, n1.value
         out = {}
-        for name, layer, dtype in _MAP_LAYERS:
-            a = np.empty((M, n0, n1) if layer < MAP_LEVEL_MAX else (M, F, n0, n1), dtype=dtype)
-            self._chk(self.lib.geoac_fan_map_fetch(self._h, layer, a.ctypes.data_as(ctypes.c_void_p)))
+        for name, layer, dtype in layers:
+            a = np.empty((M, n0, n1) if layer < first_mf else (M, F, n0, n1), dtype=dtype)
+            self._chk(getattr(self.lib, fn + "_fetch")(self._h, layer, a.ctypes.data_as(ctypes.c_void_p)))
             out[name] = a
-        out["outside"] = np.empty(M, dtype=np.uint64)
-        self._chk(self.lib.geoac_fan_map_outside(self._h, out["outside"].ctypes.data_as(ctypes.c_void_p)))
         if spec.detect_db == spec.detect_db:
             out["detect"] = np.empty((F, n0, n1), dtype=np.uint32)
-            self._chk(self.lib.geoac_fan_map_fetch_detect(self._h, out["detect"].ctypes.data_as(ctypes.c_void_p)))
+            self._chk(getattr(self.lib, fn + "_fetch_detect")(self._h, out["detect"].ctypes.data_as(ctypes.c_void_p)))
         return out
 
     def map_timing(self):
@@ -559,18 +565,7 @@ class FanContext:
         if spec is None:
             spec = tube_spec(**kw)
         self._chk(self.lib.geoac_fan_tubemap(self._h, ctypes.byref(spec)))
-        M, F, n0, n1 = (ctypes.c_int(0) for _ in range(4))
-        self._chk(self.lib.geoac_fan_tubemap_shape(self._h, *[ctypes.byref(v) for v in (M, F, n0, n1)]))
-        M, F, n0, n1 = M.value, F.value, n0.value, n1.value
-        out = {}
-        for name, layer, dtype in _TUBE_LAYERS:
-            a = np.empty((M, n0, n1) if layer < TUBE["LEVEL_MAX"] else (M, F, n0, n1), dtype=dtype)
-            self._chk(self.lib.geoac_fan_tubemap_fetch(self._h, layer, a.ctypes.data_as(ctypes.c_void_p)))
-            out[name] = a
-        if spec.detect_db == spec.detect_db:
-            out["detect"] = np.empty((F, n0, n1), dtype=np.uint32)
-            self._chk(self.lib.geoac_fan_tubemap_fetch_detect(self._h, out["detect"].ctypes.data_as(ctypes.c_void_p)))
-        return out
+        return self._fetch_layers("geoac_fan_tubemap", _TUBE_LAYERS, TUBE["LEVEL_MAX"], spec)
 
     def tubemap_timing(self):
         """HIP-event time of the last tubemap() on the context's stream [ms]"""

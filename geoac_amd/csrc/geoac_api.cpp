@@ -1597,21 +1597,12 @@ int geoac_map_view(geoac_ctx* ctx, GeoacMapView* v){
 }
 int geoac_map_fail(geoac_ctx* ctx, int code, const char* msg){ return fail(ctx, code, msg); }
 
-// ... and geoac_stations.hip (geoac_stations_int.h): the same view and the caller's launch angles in ray order
-int geoac_sta_view(geoac_ctx* ctx, GeoacStaView* v){
+// ... and geoac_stations.hip and geoac_tubemap.hip: the same view, the caller's launch angles in ray order, and the slot of the file that asks
+int geoac_launch_view(geoac_ctx* ctx, int slot, GeoacLaunchView* v){
     int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
     if(rc) return rc;
     v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
-    v->state = &ctx->sta_state;
-    return GEOAC_OK;
-}
-
-// ... and geoac_tubemap.hip (geoac_tubemap_int.h): the same again, with the tube map's slot
-int geoac_tube_view(geoac_ctx* ctx, GeoacTubeView* v){
-    int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
-    if(rc) return rc;
-    v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
-    v->state = &ctx->tube_state;
+    v->state = slot == GEOAC_SLOT_STA ? &ctx->sta_state : (slot == GEOAC_SLOT_TUBE ? &ctx->tube_state : &ctx->map_state);
     return GEOAC_OK;
 }
 

@@ -16,21 +16,11 @@
 #include <string>
 
 #include "../../include/geoac_map.h"
-#include "geoac_map_int.h"
+#include "geoac_launch_int.h"
 
 namespace {
 
 const double kMapPi = 3.141592653589793238462643;
-const unsigned long long kSign = 0x8000000000000000ull;
-
-// order-preserving key of a double: a < b as doubles (and -0 < +0) <=> key(a) < key(b) as unsigned integers
-__device__ inline unsigned long long map_key(double v){
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | kSign);
-}
-__device__ inline double map_unkey(unsigned long long k){
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~kSign) : ~k));
-}
 
 struct MapDev {
     const double* rec; const double* atten;       // the launch's tables (atten: NULL at F == 1)
@@ -44,7 +34,16 @@ struct MapDev {
     long long cells;
 };
 
-// initial values of the layers, which lie back to back in one allocation: COUNT 0 | TTIME key ~0 | CEL key 0 | LEVEL key 0 | BEST max | outside 0 | DETECT 0
+// a layer allocation (GeoacLayers) as k_map_finish and k_map_detect read it
+struct LayersDev {
+    unsigned long long *count, *ttime, *cel, *lvl, *best;
+    unsigned* detect;
+    double detect_db;
+    long long cells;
+    int M, F;
+};
+
+// initial values of the layers, which lie back to back in one allocation: COUNT 0 | TTIME key ~0 | CEL key 0 | LEVEL key 0 | BEST max | tail 0 | DETECT 0
 __global__ void k_map_fill(unsigned long long* w, long long n_mc, long long n_mfc, long long n_words){
     const long long stride = (long long)gridDim.x * blockDim.x;
     for(long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += stride){
@@ -101,11 +100,11 @@ __global__ void k_map_bin(MapDev D){
                 const long long b = m * D.cells + cell;
                 const double tt = R[GEOAC_REC_TTIME];
                 atomicAdd(&D.count[b], 1ull);
-                atomicMin(&D.ttime[b], map_key(tt));
-                atomicMax(&D.cel[b], map_key(R[GEOAC_REC_RANGE] / tt));
+                atomicMin(&D.ttime[b], geoac_key(tt));
+                atomicMax(&D.cel[b], geoac_key(R[GEOAC_REC_RANGE] / tt));
                 for(int f = 0; f < D.F; f++){
                     const double lv = D.level[(m * D.F + f) * per_m + rl];
-                    if(isfinite(lv)) atomicMax(&D.lvl[(m * D.F + f) * D.cells + cell], map_key(lv));
+                    if(isfinite(lv)) atomicMax(&D.lvl[(m * D.F + f) * D.cells + cell], geoac_key(lv));
                 }
             } else atomicAdd(&D.outside[m], 1ull);
         }
@@ -124,31 +123,31 @@ __global__ void k_map_best(MapDev D){
         const double lv = D.level[i];
         if(!isfinite(lv)) continue;
         const long long b = mf * D.cells + cell;
-        if(D.lvl[b] == map_key(lv)) atomicMin(&D.best[b], (unsigned long long)rl);
+        if(D.lvl[b] == geoac_key(lv)) atomicMin(&D.best[b], (unsigned long long)rl);
     }
 }
 
 // one thread per (m, f, cell): keys back to doubles in place, empty-cell markers
-__global__ void k_map_finish(MapDev D){
+__global__ void k_map_finish(LayersDev D){
     const long long n = D.cells * D.M * D.F;
     const long long stride = (long long)gridDim.x * blockDim.x;
     const unsigned long long p_inf = 0x7ff0000000000000ull, m_inf = 0xfff0000000000000ull;
     for(long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride){
         const unsigned long long k = D.lvl[i];
         if(k == 0ull){ D.lvl[i] = m_inf; D.best[i] = ~0ull; }
-        else D.lvl[i] = (unsigned long long)__double_as_longlong(map_unkey(k));
+        else D.lvl[i] = (unsigned long long)__double_as_longlong(geoac_unkey(k));
         const long long c = i % D.cells, mf = i / D.cells;
         if(mf % D.F == 0){
             const long long b = (mf / D.F) * D.cells + c;
             const bool any = D.count[b] != 0ull;
-            D.ttime[b] = any ? (unsigned long long)__double_as_longlong(map_unkey(D.ttime[b])) : p_inf;
-            D.cel[b] = any ? (unsigned long long)__double_as_longlong(map_unkey(D.cel[b])) : m_inf;
+            D.ttime[b] = any ? (unsigned long long)__double_as_longlong(geoac_unkey(D.ttime[b])) : p_inf;
+            D.cel[b] = any ? (unsigned long long)__double_as_longlong(geoac_unkey(D.cel[b])) : m_inf;
         }
     }
 }
 
 // one thread per (f, cell): members whose LEVEL_MAX reaches detect_db
-__global__ void k_map_detect(MapDev D){
+__global__ void k_map_detect(LayersDev D){
     const long long n = D.cells * D.F;
     const long long stride = (long long)gridDim.x * blockDim.x;
     for(long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride){
@@ -163,46 +162,21 @@ __global__ void k_map_detect(MapDev D){
 }
 
 struct MapState {
-    void* layers = nullptr; size_t layers_cap = 0;
+    GeoacLayers L{};                                     // tail: outside[M]
     double* level = nullptr; size_t level_cap = 0;
     int* cell = nullptr; size_t cell_cap = 0;
     unsigned long long map_gen = 0, level_gen = 0;       // the context's invalidation counter they were made at (0: never)
     geoac_map_spec spec{};
-    int M = 0, F = 0, n_rays = 0, legs = 0;
-    long long cells = 0;
-    bool detect = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    size_t mc() const { return (size_t)M * (size_t)cells; }
-    size_t mfc() const { return mc() * (size_t)F; }
+    EventPair ev;
 };
-
-unsigned blocks_for(long long n){ long long b = (n + 255) / 256; if(b < 1) b = 1; if(b > (1ll << 20)) b = 1ll << 20; return (unsigned)b; }
-
-int grow(void** p, size_t* cap, size_t need){
-    if(*p && *cap >= need) return GEOAC_OK;
-    if(*p){ hipFree(*p); *p = nullptr; *cap = 0; }                  // (hipFree waits for the work that may still read it)
-    if(hipMalloc(p, need) != hipSuccess){ (void)hipGetLastError(); *p = nullptr; return GEOAC_E_NOMEM; }
-    *cap = need;
-    return GEOAC_OK;
-}
-
-bool spherical(int eqset){ return eqset == GEOAC_EQ_GLOBAL || eqset == GEOAC_EQ_GLOBAL_RNGDEP; }
 
 // the first thing wrong with a spec, or NULL
 const char* spec_fault(int eqset, const geoac_map_spec* s){
     if(eqset < GEOAC_EQ_2D || eqset > GEOAC_EQ_GLOBAL_RNGDEP) return "unknown equation set";
     if(!s) return "spec is NULL";
-    for(int a = 0; a < 2; a++){
-        if(!std::isfinite(s->origin[a])) return "origin must be finite";
-        if(!std::isfinite(s->step[a]) || !(s->step[a] > 0.0)) return "step must be finite and greater than 0";
-        if(s->n[a] < 1) return "n must be at least 1 per axis";
-    }
-    if((long long)s->n[0] * s->n[1] > (long long)GEOAC_MAP_MAX_CELLS) return "n[0] * n[1] exceeds GEOAC_MAP_MAX_CELLS (2^24)";
+    if(const char* f = geoac_grid_fault(eqset, s->origin, s->step, s->n, s->wrap_lon, s->turn_min, s->turn_max)) return f;
     if(eqset == GEOAC_EQ_2D && s->n[1] != 1) return "the 2-D set has one axis (range): n[1] must be 1";
-    if(s->wrap_lon != 0 && s->wrap_lon != 1) return "wrap_lon must be 0 or 1";
-    if(s->wrap_lon && !spherical(eqset)) return "wrap_lon is for the spherical sets only (a Cartesian set has no longitude)";
     if(s->leg_min < 0 || s->leg_max < s->leg_min) return "legs: need 0 <= leg_min <= leg_max";
-    if(std::isnan(s->turn_min) || std::isnan(s->turn_max) || !(s->turn_min < s->turn_max)) return "turning-height band: need turn_min < turn_max, neither NaN (-inf / +inf: no bound)";
     return nullptr;
 }
 
@@ -210,23 +184,14 @@ struct Bound { geoac_ctx* ctx; GeoacMapView v; MapState* st; };
 
 // view of the context + its map state (created on first use); `what` names the caller in messages
 int bind(geoac_ctx* ctx, const char* what, bool create, Bound* b){
-    if(!ctx) return GEOAC_E_INVALID;
-    b->ctx = ctx;
-    int rc = geoac_map_view(ctx, &b->v);
+    GeoacLaunchView lv;
+    int rc = bind_launch(ctx, what, GEOAC_SLOT_MAP, &lv);
     if(rc) return rc;
-    if(!b->v.fresh)
-        return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": no completed launch, or new angles, an atmosphere upload, geoac_set_sources or "
-                                                     "geoac_set_frequencies have come since it (launch again)").c_str());
-    if(!*b->v.state && create) *b->v.state = new MapState();
-    b->st = (MapState*)*b->v.state;
-    if(hipSetDevice(b->v.device) != hipSuccess) return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": hipSetDevice failed").c_str());
+    b->ctx = ctx; b->v = lv.map;
+    if(!*lv.state && create) *lv.state = new MapState();
+    b->st = (MapState*)*lv.state;
     return GEOAC_OK;
 }
-
-int hip_fail(geoac_ctx* ctx, const char* what, hipError_t e){
-    return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define MAPCHK(what, call) do { hipError_t e_ = (call); if(e_ != hipSuccess) return hip_fail(b.ctx, what, e_); } while(0)
 
 void fill_dev(const Bound& b, MapDev* D){
     const GeoacMapView& v = b.v; MapState* st = b.st;
@@ -244,8 +209,8 @@ int ensure_level(Bound& b, const char* what){
     if(grow((void**)&st->level, &st->level_cap, sizeof(double) * (size_t)n))
         return geoac_map_fail(b.ctx, GEOAC_E_NOMEM, (std::string(what) + ": no device memory for the level table").c_str());
     MapDev D; fill_dev(b, &D);
-    hipLaunchKernelGGL(k_map_level, dim3(blocks_for(n)), dim3(256), 0, (hipStream_t)v.stream, D);
-    MAPCHK(what, hipGetLastError());
+    hipLaunchKernelGGL(k_map_level, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)v.stream, D);
+    GEOAC_CHK(what, hipGetLastError());
     st->level_gen = v.gen;
     return GEOAC_OK;
 }
@@ -259,9 +224,25 @@ int bind_map(geoac_ctx* ctx, const char* what, Bound* b){
     return GEOAC_OK;
 }
 
-// byte offset and size of a layer inside the allocation
-void layer_span(const MapState* st, int layer, size_t* off, size_t* bytes){
-    const size_t mc = st->mc() * 8, mfc = st->mfc() * 8;
+LayersDev layers_dev(const GeoacLayers* L, double detect_db){
+    LayersDev D{};
+    char* base = (char*)L->base;
+    size_t off, bytes;
+    geoac_layers_span(L, GEOAC_MAP_COUNT, &off, &bytes);     D.count = (unsigned long long*)(base + off);
+    geoac_layers_span(L, GEOAC_MAP_TTIME_MIN, &off, &bytes); D.ttime = (unsigned long long*)(base + off);
+    geoac_layers_span(L, GEOAC_MAP_CEL_MAX, &off, &bytes);   D.cel = (unsigned long long*)(base + off);
+    geoac_layers_span(L, GEOAC_MAP_LEVEL_MAX, &off, &bytes); D.lvl = (unsigned long long*)(base + off);
+    geoac_layers_span(L, GEOAC_MAP_BEST, &off, &bytes);      D.best = (unsigned long long*)(base + off);
+    geoac_layers_detect_span(L, &off, &bytes);               D.detect = (unsigned*)(base + off);
+    D.detect_db = detect_db; D.cells = L->cells; D.M = L->M; D.F = L->F;
+    return D;
+}
+
+}  // namespace
+
+// ---- the layer allocation (geoac_map_int.h), for geoac_tubemap.hip as well ----
+void geoac_layers_span(const GeoacLayers* L, int layer, size_t* off, size_t* bytes){
+    const size_t mc = (size_t)L->M * (size_t)L->cells * 8, mfc = mc * (size_t)L->F;
     switch(layer){
     case GEOAC_MAP_COUNT:     *off = 0;            *bytes = mc;  break;
     case GEOAC_MAP_TTIME_MIN: *off = mc;           *bytes = mc;  break;
@@ -270,26 +251,89 @@ void layer_span(const MapState* st, int layer, size_t* off, size_t* bytes){
     default:                  *off = 3 * mc + mfc; *bytes = mfc; break;
     }
 }
-size_t outside_off(const MapState* st){ return 3 * st->mc() * 8 + 2 * st->mfc() * 8; }
-size_t detect_off(const MapState* st){ return outside_off(st) + (size_t)st->M * 8; }
-size_t detect_bytes(const MapState* st){ return (size_t)st->F * (size_t)st->cells * 4; }
+void geoac_layers_tail_span(const GeoacLayers* L, size_t* off, size_t* bytes){
+    size_t o, n;
+    geoac_layers_span(L, GEOAC_MAP_BEST, &o, &n);
+    *off = o + n; *bytes = (size_t)L->tail_words * 8;
+}
+void geoac_layers_detect_span(const GeoacLayers* L, size_t* off, size_t* bytes){
+    size_t o, n;
+    geoac_layers_tail_span(L, &o, &n);
+    *off = o + n; *bytes = (size_t)L->F * (size_t)L->cells * 4;
+}
+size_t geoac_layers_bytes(const GeoacLayers* L){
+    size_t off, n;
+    geoac_layers_detect_span(L, &off, &n);
+    return off + ((n + 7) & ~(size_t)7);
+}
+int geoac_layers_grow(GeoacLayers* L){ return grow(&L->base, &L->cap, geoac_layers_bytes(L)); }
 
-int fetch(Bound& b, const char* what, void* host, size_t off, size_t bytes){
-    MAPCHK(what, hipMemcpyAsync(host, (const char*)b.st->layers + off, bytes, hipMemcpyDeviceToHost, (hipStream_t)b.v.stream));
-    MAPCHK(what, hipStreamSynchronize((hipStream_t)b.v.stream));
-    return GEOAC_OK;
+void geoac_layers_fill(const GeoacLayers* L, void* stream){
+    const long long n_mc = (long long)L->M * L->cells, n_mfc = n_mc * L->F, n_words = (long long)(geoac_layers_bytes(L) / 8);
+    hipLaunchKernelGGL(k_map_fill, dim3(blocks_for(n_words, 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long*)L->base, n_mc, n_mfc, n_words);
+}
+void geoac_layers_finish(const GeoacLayers* L, void* stream){
+    hipLaunchKernelGGL(k_map_finish, dim3(blocks_for((long long)L->M * L->F * L->cells, 256)), dim3(256), 0, (hipStream_t)stream, layers_dev(L, 0.0));
+}
+void geoac_layers_detect(const GeoacLayers* L, double detect_db, void* stream){
+    hipLaunchKernelGGL(k_map_detect, dim3(blocks_for(L->cells * L->F, 256)), dim3(256), 0, (hipStream_t)stream, layers_dev(L, detect_db));
 }
 
-}  // namespace
+static int fetch_span(geoac_ctx* ctx, const char* what, const GeoacLayers* L, void* stream, void* host, size_t off, size_t bytes){
+    hipError_t e = hipMemcpyAsync(host, (const char*)L->base + off, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream);
+    if(e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    return e == hipSuccess ? GEOAC_OK : hip_fail(ctx, what, e);
+}
+
+int geoac_layers_dev(geoac_ctx* ctx, const char* what, const GeoacLayers* L, int layer, void** dev_ptr, size_t* bytes){
+    if(layer < 0 || layer >= GEOAC_MAP_LAYERS) return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": unknown layer").c_str());
+    size_t off, n;
+    geoac_layers_span(L, layer, &off, &n);
+    if(dev_ptr) *dev_ptr = (char*)L->base + off;
+    if(bytes) *bytes = n;
+    return GEOAC_OK;
+}
+int geoac_layers_fetch(geoac_ctx* ctx, const char* what, const GeoacLayers* L, void* stream, int layer, void* host){
+    if(layer < 0 || layer >= GEOAC_MAP_LAYERS || !host) return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": unknown layer / NULL buffer").c_str());
+    size_t off, n;
+    geoac_layers_span(L, layer, &off, &n);
+    return fetch_span(ctx, what, L, stream, host, off, n);
+}
+int geoac_layers_fetch_detect(geoac_ctx* ctx, const char* what, const char* noun, const GeoacLayers* L, void* stream, uint32_t* host){
+    if(!host) return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": NULL buffer").c_str());
+    if(!L->detect) return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": the " + noun + " was made without a detection threshold (detect_db = NaN)").c_str());
+    size_t off, n;
+    geoac_layers_detect_span(L, &off, &n);
+    return fetch_span(ctx, what, L, stream, host, off, n);
+}
+int geoac_layers_fetch_tail(geoac_ctx* ctx, const char* what, const GeoacLayers* L, void* stream, void* host){
+    if(!host) return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": NULL buffer").c_str());
+    size_t off, n;
+    geoac_layers_tail_span(L, &off, &n);
+    return fetch_span(ctx, what, L, stream, host, off, n);
+}
+
+// ---- the grid and the turning-height band of a spec, for geoac_tubemap.hip as well ----
+const char* geoac_grid_fault(int eqset, const double origin[2], const double step[2], const int n[2], int wrap_lon, double turn_min, double turn_max){
+    for(int a = 0; a < 2; a++){
+        if(!std::isfinite(origin[a])) return "origin must be finite";
+        if(!std::isfinite(step[a]) || !(step[a] > 0.0)) return "step must be finite and greater than 0";
+        if(n[a] < 1) return "n must be at least 1 per axis";
+    }
+    if((long long)n[0] * n[1] > (long long)GEOAC_MAP_MAX_CELLS) return "n[0] * n[1] exceeds GEOAC_MAP_MAX_CELLS (2^24)";
+    if(wrap_lon != 0 && wrap_lon != 1) return "wrap_lon must be 0 or 1";
+    if(wrap_lon && !spherical(eqset)) return "wrap_lon is for the spherical sets only (a Cartesian set has no longitude)";
+    if(std::isnan(turn_min) || std::isnan(turn_max) || !(turn_min < turn_max)) return "turning-height band: need turn_min < turn_max, neither NaN (-inf / +inf: no bound)";
+    return nullptr;
+}
 
 extern "C" void geoac_map_release(void* state){
     MapState* st = (MapState*)state;
     if(!st) return;
-    if(st->layers) hipFree(st->layers);
+    if(st->L.base) hipFree(st->L.base);
     if(st->level) hipFree(st->level);
     if(st->cell) hipFree(st->cell);
-    if(st->e0) hipEventDestroy(st->e0);
-    if(st->e1) hipEventDestroy(st->e1);
+    st->ev.release();
     delete st;
 }
 
@@ -308,38 +352,30 @@ extern "C" int geoac_fan_map(geoac_ctx* ctx, const geoac_map_spec* spec){
     MapState* st = b.st; const GeoacMapView& v = b.v;
     hipStream_t s = (hipStream_t)v.stream;
     st->map_gen = 0;                                   // (no current map until this one is complete)
-    if(!st->e0){ MAPCHK(what, hipEventCreate(&st->e0)); MAPCHK(what, hipEventCreate(&st->e1)); }
-    MAPCHK(what, hipEventRecord(st->e0, s));
+    GEOAC_CHK(what, st->ev.start(s));
     if((rc = ensure_level(b, what))) return rc;
-    st->spec = *spec; st->M = v.M; st->F = v.F; st->n_rays = v.n_rays; st->legs = v.legs;
-    st->cells = (long long)spec->n[0] * spec->n[1];
-    st->detect = !std::isnan(spec->detect_db);
+    st->spec = *spec;
+    GeoacLayers& L = st->L;
+    L.M = v.M; L.F = v.F; L.cells = (long long)spec->n[0] * spec->n[1]; L.tail_words = v.M; L.detect = !std::isnan(spec->detect_db);
     const long long n_rec = (long long)v.M * v.n_rays * v.legs;
-    const size_t need = detect_off(st) + ((detect_bytes(st) + 7) & ~(size_t)7);
-    if(grow(&st->layers, &st->layers_cap, need) || grow((void**)&st->cell, &st->cell_cap, sizeof(int) * (size_t)n_rec))
-        return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_map: no device memory for the layers (" + std::to_string(need >> 20) + " MiB for " + std::to_string(v.M) + " members x " +
-                                                   std::to_string(v.F) + " frequencies x " + std::to_string(st->cells) + " cells)").c_str());
+    if(geoac_layers_grow(&L) || grow((void**)&st->cell, &st->cell_cap, sizeof(int) * (size_t)n_rec))
+        return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_map: no device memory for the layers (" + std::to_string(geoac_layers_bytes(&L) >> 20) + " MiB for " + std::to_string(v.M) + " members x " +
+                                                   std::to_string(v.F) + " frequencies x " + std::to_string(L.cells) + " cells)").c_str());
     MapDev D; fill_dev(b, &D);
-    char* base = (char*)st->layers;
+    const LayersDev P = layers_dev(&L, spec->detect_db);
+    D.count = P.count; D.ttime = P.ttime; D.cel = P.cel; D.lvl = P.lvl; D.best = P.best; D.detect = P.detect;
     size_t off, bytes;
-    layer_span(st, GEOAC_MAP_COUNT, &off, &bytes);     D.count = (unsigned long long*)(base + off);
-    layer_span(st, GEOAC_MAP_TTIME_MIN, &off, &bytes); D.ttime = (unsigned long long*)(base + off);
-    layer_span(st, GEOAC_MAP_CEL_MAX, &off, &bytes);   D.cel = (unsigned long long*)(base + off);
-    layer_span(st, GEOAC_MAP_LEVEL_MAX, &off, &bytes); D.lvl = (unsigned long long*)(base + off);
-    layer_span(st, GEOAC_MAP_BEST, &off, &bytes);      D.best = (unsigned long long*)(base + off);
-    D.outside = (unsigned long long*)(base + outside_off(st));
-    D.detect = (unsigned*)(base + detect_off(st));
+    geoac_layers_tail_span(&L, &off, &bytes);          D.outside = (unsigned long long*)((char*)L.base + off);
     D.o0 = spec->origin[0]; D.o1 = spec->origin[1]; D.s0 = spec->step[0]; D.s1 = spec->step[1]; D.n0 = spec->n[0]; D.n1 = spec->n[1];
     D.wrap = spec->wrap_lon; D.leg_min = spec->leg_min; D.leg_max = spec->leg_max; D.turn_min = spec->turn_min; D.turn_max = spec->turn_max;
-    D.detect_db = spec->detect_db; D.cells = st->cells;
-    const long long n_mc = (long long)st->mc(), n_mfc = (long long)st->mfc(), n_words = (long long)(need / 8);
-    hipLaunchKernelGGL(k_map_fill, dim3(blocks_for(n_words)), dim3(256), 0, s, (unsigned long long*)st->layers, n_mc, n_mfc, n_words);
-    hipLaunchKernelGGL(k_map_bin, dim3(blocks_for(n_rec)), dim3(256), 0, s, D);
-    hipLaunchKernelGGL(k_map_best, dim3(blocks_for(n_rec * v.F)), dim3(256), 0, s, D);
-    hipLaunchKernelGGL(k_map_finish, dim3(blocks_for(n_mfc)), dim3(256), 0, s, D);
-    if(st->detect) hipLaunchKernelGGL(k_map_detect, dim3(blocks_for(st->cells * v.F)), dim3(256), 0, s, D);
-    MAPCHK(what, hipGetLastError());
-    MAPCHK(what, hipEventRecord(st->e1, s));
+    D.detect_db = spec->detect_db; D.cells = L.cells;
+    geoac_layers_fill(&L, s);
+    hipLaunchKernelGGL(k_map_bin, dim3(blocks_for(n_rec, 256)), dim3(256), 0, s, D);
+    hipLaunchKernelGGL(k_map_best, dim3(blocks_for(n_rec * v.F, 256)), dim3(256), 0, s, D);
+    geoac_layers_finish(&L, s);
+    if(L.detect) geoac_layers_detect(&L, spec->detect_db, s);
+    GEOAC_CHK(what, hipGetLastError());
+    GEOAC_CHK(what, st->ev.stop(s));
     st->map_gen = v.gen;
     return GEOAC_OK;
 }
@@ -348,8 +384,8 @@ extern "C" int geoac_fan_map_shape(geoac_ctx* ctx, int* n_members, int* n_freq, 
     Bound b;
     int rc = bind_map(ctx, "fan_map_shape", &b);
     if(rc) return rc;
-    if(n_members) *n_members = b.st->M;
-    if(n_freq) *n_freq = b.st->F;
+    if(n_members) *n_members = b.st->L.M;
+    if(n_freq) *n_freq = b.st->L.F;
     if(n0) *n0 = b.st->spec.n[0];
     if(n1) *n1 = b.st->spec.n[1];
     return GEOAC_OK;
@@ -358,40 +394,25 @@ extern "C" int geoac_fan_map_shape(geoac_ctx* ctx, int* n_members, int* n_freq, 
 extern "C" int geoac_fan_map_dev(geoac_ctx* ctx, int layer, void** dev_ptr, size_t* bytes){
     Bound b;
     int rc = bind_map(ctx, "fan_map_dev", &b);
-    if(rc) return rc;
-    if(layer < 0 || layer >= GEOAC_MAP_LAYERS) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_map_dev: unknown layer");
-    size_t off, n;
-    layer_span(b.st, layer, &off, &n);
-    if(dev_ptr) *dev_ptr = (char*)b.st->layers + off;
-    if(bytes) *bytes = n;
-    return GEOAC_OK;
+    return rc ? rc : geoac_layers_dev(ctx, "fan_map_dev", &b.st->L, layer, dev_ptr, bytes);
 }
 
 extern "C" int geoac_fan_map_fetch(geoac_ctx* ctx, int layer, void* host){
     Bound b;
     int rc = bind_map(ctx, "fan_map_fetch", &b);
-    if(rc) return rc;
-    if(layer < 0 || layer >= GEOAC_MAP_LAYERS || !host) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_map_fetch: unknown layer / NULL buffer");
-    size_t off, n;
-    layer_span(b.st, layer, &off, &n);
-    return fetch(b, "fan_map_fetch", host, off, n);
+    return rc ? rc : geoac_layers_fetch(ctx, "fan_map_fetch", &b.st->L, b.v.stream, layer, host);
 }
 
 extern "C" int geoac_fan_map_fetch_detect(geoac_ctx* ctx, uint32_t* detect_host){
     Bound b;
     int rc = bind_map(ctx, "fan_map_fetch_detect", &b);
-    if(rc) return rc;
-    if(!detect_host) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_map_fetch_detect: NULL buffer");
-    if(!b.st->detect) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_map_fetch_detect: the map was made without a detection threshold (detect_db = NaN)");
-    return fetch(b, "fan_map_fetch_detect", detect_host, detect_off(b.st), detect_bytes(b.st));
+    return rc ? rc : geoac_layers_fetch_detect(ctx, "fan_map_fetch_detect", "map", &b.st->L, b.v.stream, detect_host);
 }
 
 extern "C" int geoac_fan_map_outside(geoac_ctx* ctx, uint64_t* outside_host){
     Bound b;
     int rc = bind_map(ctx, "fan_map_outside", &b);
-    if(rc) return rc;
-    if(!outside_host) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_map_outside: NULL buffer");
-    return fetch(b, "fan_map_outside", outside_host, outside_off(b.st), (size_t)b.st->M * 8);
+    return rc ? rc : geoac_layers_fetch_tail(ctx, "fan_map_outside", &b.st->L, b.v.stream, outside_host);
 }
 
 extern "C" int geoac_fan_map_timing(geoac_ctx* ctx, double* ms){
@@ -399,10 +420,7 @@ extern "C" int geoac_fan_map_timing(geoac_ctx* ctx, double* ms){
     int rc = bind_map(ctx, "fan_map_timing", &b);
     if(rc) return rc;
     if(!ms) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_map_timing: NULL argument");
-    MAPCHK("fan_map_timing", hipEventSynchronize(b.st->e1));
-    float t = 0;
-    MAPCHK("fan_map_timing", hipEventElapsedTime(&t, b.st->e0, b.st->e1));
-    *ms = t;
+    GEOAC_CHK("fan_map_timing", b.st->ev.ms(ms));
     return GEOAC_OK;
 }
 
@@ -423,7 +441,7 @@ extern "C" int geoac_fan_fetch_level(geoac_ctx* ctx, double* level_host){
     if(!level_host) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_fetch_level: NULL buffer");
     if((rc = ensure_level(b, "fan_fetch_level"))) return rc;
     const size_t n = sizeof(double) * (size_t)b.v.M * b.v.F * b.v.n_rays * b.v.legs;
-    MAPCHK("fan_fetch_level", hipMemcpyAsync(level_host, b.st->level, n, hipMemcpyDeviceToHost, (hipStream_t)b.v.stream));
-    MAPCHK("fan_fetch_level", hipStreamSynchronize((hipStream_t)b.v.stream));
+    GEOAC_CHK("fan_fetch_level", hipMemcpyAsync(level_host, b.st->level, n, hipMemcpyDeviceToHost, (hipStream_t)b.v.stream));
+    GEOAC_CHK("fan_fetch_level", hipStreamSynchronize((hipStream_t)b.v.stream));
     return GEOAC_OK;
 }

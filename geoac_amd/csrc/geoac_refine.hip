@@ -23,7 +23,10 @@
 #include <vector>
 
 #include "../../include/geoac_refine.h"
+#include "geoac_launch_int.h"
+#include "geoac_stations_int.h"
 #include "geoac_refine_int.h"
+#include "geoac_tri_rule.h"
 
 #pragma clang fp contract(off)
 
@@ -77,9 +80,8 @@ __device__ inline double rfn_asin(double s){
     for(int k = 1; k <= 30; k++){ t = ((t * x2) * (double)((2 * k - 1) * (2 * k - 1))) / (double)((2 * k) * (2 * k + 1)); a = a + t; }
     return low ? a : kRfnPi / 2.0 - 2.0 * a;
 }
-__device__ inline double rfn_wrap(double d){ return d - 360.0 * floor((d + 180.0) / 360.0); }
 __device__ inline double rfn_dist(double lat1, double lon1, double lat2, double lon2, double R){
-    const double a = rfn_sin(((lat2 - lat1) * kRfnPi / 180.0) / 2.0), b = rfn_sin((rfn_wrap(lon2 - lon1) * kRfnPi / 180.0) / 2.0);
+    const double a = rfn_sin(((lat2 - lat1) * kRfnPi / 180.0) / 2.0), b = rfn_sin((wrap180(lon2 - lon1) * kRfnPi / 180.0) / 2.0);
     double h = a * a + (rfn_cos(lat1 * kRfnPi / 180.0) * rfn_cos(lat2 * kRfnPi / 180.0)) * (b * b);
     if(h > 1.0) h = 1.0;
     return (2.0 * R) * rfn_asin(sqrt(h));
@@ -124,7 +126,7 @@ __device__ inline bool rfn_newton(const RfnDev& D, const double* R, double s0, d
     double e0, e1, a00, a01, a10, a11;
     if(D.spherical){
         e0 = s0 * kRfnPi / 180.0 - S[1];
-        e1 = rfn_wrap(s1 - S[2] * 180.0 / kRfnPi) * kRfnPi / 180.0;
+        e1 = wrap180(s1 - S[2] * 180.0 / kRfnPi) * kRfnPi / 180.0;
         const double q = 1.0 / D.rg, qc = 1.0 / (D.rg * rfn_cos(S[1]));
         a00 = S[7] - ((q * S[4]) / S[3]) * S[6];    a01 = S[13] - ((q * S[4]) / S[3]) * S[12];
         a10 = S[8] - ((qc * S[5]) / S[3]) * S[6];   a11 = S[14] - ((qc * S[5]) / S[3]) * S[12];
@@ -238,12 +240,10 @@ struct RfnState {
     int n_seeds = 0, F = 0, launches = 0;
     double ms_launch = 0.0, ms_kernels = 0.0;
     uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair ev;
     size_t rows_bytes() const { return sizeof(double) * (size_t)n_seeds * GEOAC_RFN_STRIDE; }
     size_t level_bytes() const { return sizeof(double) * (size_t)n_seeds * F; }
 };
-
-bool spherical(int eqset){ return eqset == GEOAC_EQ_GLOBAL || eqset == GEOAC_EQ_GLOBAL_RNGDEP; }
 
 const char* spec_fault(int eqset, const geoac_refine_spec* s, int* code){
     *code = GEOAC_E_INVALID;
@@ -262,6 +262,7 @@ const char* spec_fault(int eqset, const geoac_refine_spec* s, int* code){
 
 struct Bound { geoac_ctx* ctx; GeoacRfnView v; RfnState* st; };
 
+// (not bind_launch: geoac_fan_refine has its own message for a context without a current launch, and the fetches ask for a current result)
 int bind(geoac_ctx* ctx, const char* what, bool create, Bound* b){
     if(!ctx) return GEOAC_E_INVALID;
     b->ctx = ctx;
@@ -283,18 +284,7 @@ int bind_result(geoac_ctx* ctx, const char* what, Bound* b){
     return GEOAC_OK;
 }
 
-int hip_fail(geoac_ctx* ctx, const char* what, hipError_t e){
-    return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define RFNCHK(what, call) do { hipError_t e_ = (call); if(e_ != hipSuccess) return hip_fail(b.ctx, what, e_); } while(0)
-
 size_t up256(size_t n){ return (n + 255) / 256 * 256; }
-unsigned blocks_for(long long n, int per_block){
-    long long k = (n + per_block - 1) / per_block;
-    if(k < 1) k = 1;
-    if(k > (1ll << 20)) k = 1ll << 20;
-    return (unsigned)k;
-}
 
 }  // namespace
 
@@ -302,8 +292,7 @@ extern "C" void geoac_rfn_release(void* state){
     RfnState* st = (RfnState*)state;
     if(!st) return;
     if(st->buf) hipFree(st->buf);
-    if(st->e0) hipEventDestroy(st->e0);
-    if(st->e1) hipEventDestroy(st->e1);
+    st->ev.release();
     delete st;
 }
 
@@ -340,8 +329,8 @@ extern "C" int geoac_fan_refine(geoac_ctx* ctx, const geoac_refine_spec* spec){
     // seeds before every list: integer prefix counts of min(hits, cap), on the host
     const long long n_lists = (long long)M * n_sta;
     std::vector<unsigned> hits((size_t)n_lists);
-    RFNCHK(what, hipMemcpyAsync(hits.data(), d_hits, sizeof(unsigned) * (size_t)n_lists, hipMemcpyDeviceToHost, s));
-    RFNCHK(what, hipStreamSynchronize(s));
+    GEOAC_CHK(what, hipMemcpyAsync(hits.data(), d_hits, sizeof(unsigned) * (size_t)n_lists, hipMemcpyDeviceToHost, s));
+    GEOAC_CHK(what, hipStreamSynchronize(s));
     st->h_offs.resize((size_t)n_lists);
     long long n_seeds = 0;
     for(long long l = 0; l < n_lists; l++){
@@ -365,11 +354,7 @@ extern "C" int geoac_fan_refine(geoac_ctx* ctx, const geoac_refine_spec* spec){
                  o_mem = carve(sizeof(double) * GEOAC_RFN_MEMW * (size_t)M), o_meta = carve(sizeof(int) * 4 * N), o_trial = carve(sizeof(double) * 2 * N),
                  o_best = carve(sizeof(double) * 5 * N), o_state = carve(sizeof(int) * 3 * N), o_active = carve(sizeof(unsigned)),
                  o_rows = carve(sizeof(double) * GEOAC_RFN_STRIDE * N), o_level = carve(sizeof(double) * (size_t)F * N);
-    if(!st->buf || st->buf_cap < off){
-        if(st->buf){ hipFree(st->buf); st->buf = nullptr; st->buf_cap = 0; }
-        if(hipMalloc(&st->buf, off) != hipSuccess){ (void)hipGetLastError(); st->buf = nullptr; return geoac_map_fail(ctx, GEOAC_E_NOMEM, "fan_refine: no device memory for the seeds"); }
-        st->buf_cap = off;
-    }
+    if(grow(&st->buf, &st->buf_cap, off)) return geoac_map_fail(ctx, GEOAC_E_NOMEM, "fan_refine: no device memory for the seeds");
     char* base = (char*)st->buf;
     st->args = (RfnDev*)(base + o_args);
     RfnDev& D = st->h;
@@ -383,21 +368,20 @@ extern "C" int geoac_fan_refine(geoac_ctx* ctx, const geoac_refine_spec* spec){
     D.M = M; D.F = F; D.n_sta = n_sta; D.cap = cap; D.n_seeds = (int)n_seeds; D.legs = b.v.map.legs; D.n_lists = n_lists;
     st->h_mem.assign(b.v.mem, b.v.mem + (size_t)M * GEOAC_RFN_MEMW);
     st->h_trial.resize(2 * N);
-    if(!st->e0){ RFNCHK(what, hipEventCreate(&st->e0)); RFNCHK(what, hipEventCreate(&st->e1)); }
-    RFNCHK(what, hipMemcpyAsync(st->args, &D, sizeof(RfnDev), hipMemcpyHostToDevice, s));
-    RFNCHK(what, hipMemcpyAsync(base + o_offs, st->h_offs.data(), sizeof(unsigned) * (size_t)n_lists, hipMemcpyHostToDevice, s));
-    RFNCHK(what, hipMemcpyAsync(base + o_sta, d_sta, sizeof(double) * 2 * (size_t)n_sta, hipMemcpyDeviceToDevice, s));
-    RFNCHK(what, hipMemcpyAsync(base + o_mem, st->h_mem.data(), sizeof(double) * st->h_mem.size(), hipMemcpyHostToDevice, s));
+    GEOAC_CHK(what, hipMemcpyAsync(st->args, &D, sizeof(RfnDev), hipMemcpyHostToDevice, s));
+    GEOAC_CHK(what, hipMemcpyAsync(base + o_offs, st->h_offs.data(), sizeof(unsigned) * (size_t)n_lists, hipMemcpyHostToDevice, s));
+    GEOAC_CHK(what, hipMemcpyAsync(base + o_sta, d_sta, sizeof(double) * 2 * (size_t)n_sta, hipMemcpyDeviceToDevice, s));
+    GEOAC_CHK(what, hipMemcpyAsync(base + o_mem, st->h_mem.data(), sizeof(double) * st->h_mem.size(), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_rfn_seed, dim3(blocks_for(n_lists * cap, 256)), dim3(256), 0, s, (const RfnDev*)st->args);
-    RFNCHK(what, hipGetLastError());
+    GEOAC_CHK(what, hipGetLastError());
 
     const unsigned n_blk = blocks_for(n_seeds, 64);
     GeoacMapView mv{};
     unsigned active = 1;
     for(int round = 1; round <= spec->max_iter && active > 0; round++){
         // the trial angles: device -> host -> geoac_fan_set_angles (16 bytes per seed)
-        RFNCHK(what, hipMemcpyAsync(st->h_trial.data(), D.trial, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, s));
-        RFNCHK(what, hipStreamSynchronize(s));
+        GEOAC_CHK(what, hipMemcpyAsync(st->h_trial.data(), D.trial, sizeof(double) * 2 * N, hipMemcpyDeviceToHost, s));
+        GEOAC_CHK(what, hipStreamSynchronize(s));
         if((rc = geoac_fan_set_angles(ctx, (int)n_seeds, st->h_trial.data(), st->h_trial.data() + N))) return rc;
         if((rc = geoac_fan_launch(ctx))) return rc;
         st->launches = round;
@@ -406,26 +390,26 @@ extern "C" int geoac_fan_refine(geoac_ctx* ctx, const geoac_refine_spec* spec){
         if(geoac_last_timing(ctx, ms3, st3) == GEOAC_OK) st->ms_launch += ms3[0];
         if((rc = geoac_map_view(ctx, &mv))) return rc;
         if(mv.M != M || mv.n_rays != (int)n_seeds || mv.legs != D.legs) return geoac_map_fail(ctx, GEOAC_E_HIP, "fan_refine: the round's launch does not have the shape of the seeds");
-        RFNCHK(what, hipEventRecord(st->e0, s));
-        RFNCHK(what, hipMemsetAsync(D.active, 0, sizeof(unsigned), s));
+        GEOAC_CHK(what, st->ev.start(s));
+        GEOAC_CHK(what, hipMemsetAsync(D.active, 0, sizeof(unsigned), s));
         hipLaunchKernelGGL(k_rfn_step, dim3(n_blk), dim3(64), 0, s, (const RfnDev*)st->args, mv.rec, round);
-        RFNCHK(what, hipGetLastError());
-        RFNCHK(what, hipEventRecord(st->e1, s));
-        RFNCHK(what, hipMemcpyAsync(&active, D.active, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        RFNCHK(what, hipStreamSynchronize(s));
-        float t = 0; RFNCHK(what, hipEventElapsedTime(&t, st->e0, st->e1));
+        GEOAC_CHK(what, hipGetLastError());
+        GEOAC_CHK(what, st->ev.stop(s));
+        GEOAC_CHK(what, hipMemcpyAsync(&active, D.active, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        GEOAC_CHK(what, hipStreamSynchronize(s));
+        double t = 0; GEOAC_CHK(what, st->ev.ms(&t));
         st->ms_kernels += t;
     }
     void* level = nullptr; size_t level_bytes = 0;
     if((rc = geoac_fan_level_dev(ctx, &level, &level_bytes))) return rc;         // (formed on first use after a launch, geoac_map.hip)
-    RFNCHK(what, hipEventRecord(st->e0, s));
+    GEOAC_CHK(what, st->ev.start(s));
     hipLaunchKernelGGL(k_rfn_rows, dim3(n_blk), dim3(64), 0, s, (const RfnDev*)st->args, mv.rec, (const double*)level);
-    RFNCHK(what, hipGetLastError());
-    RFNCHK(what, hipEventRecord(st->e1, s));
+    GEOAC_CHK(what, hipGetLastError());
+    GEOAC_CHK(what, st->ev.stop(s));
     std::vector<int> status(N);
-    RFNCHK(what, hipMemcpyAsync(status.data(), D.state, sizeof(int) * N, hipMemcpyDeviceToHost, s));
-    RFNCHK(what, hipStreamSynchronize(s));
-    float t = 0; RFNCHK(what, hipEventElapsedTime(&t, st->e0, st->e1));
+    GEOAC_CHK(what, hipMemcpyAsync(status.data(), D.state, sizeof(int) * N, hipMemcpyDeviceToHost, s));
+    GEOAC_CHK(what, hipStreamSynchronize(s));
+    double t = 0; GEOAC_CHK(what, st->ev.ms(&t));
     st->ms_kernels += t;
     for(size_t i = 0; i < N; i++){
         const int c = status[i];
@@ -465,9 +449,9 @@ extern "C" int geoac_fan_refine_fetch(geoac_ctx* ctx, double* rows, double* leve
     const RfnState* st = b.st;
     if(st->n_seeds == 0) return GEOAC_OK;
     hipStream_t s = (hipStream_t)b.v.map.stream;
-    if(rows) RFNCHK(what, hipMemcpyAsync(rows, st->h.rows, st->rows_bytes(), hipMemcpyDeviceToHost, s));
-    if(level) RFNCHK(what, hipMemcpyAsync(level, st->h.lvl, st->level_bytes(), hipMemcpyDeviceToHost, s));
-    RFNCHK(what, hipStreamSynchronize(s));
+    if(rows) GEOAC_CHK(what, hipMemcpyAsync(rows, st->h.rows, st->rows_bytes(), hipMemcpyDeviceToHost, s));
+    if(level) GEOAC_CHK(what, hipMemcpyAsync(level, st->h.lvl, st->level_bytes(), hipMemcpyDeviceToHost, s));
+    GEOAC_CHK(what, hipStreamSynchronize(s));
     return GEOAC_OK;
 }
 

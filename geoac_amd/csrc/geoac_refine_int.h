@@ -20,7 +20,5 @@ struct GeoacRfnView {
 
 extern "C" int  geoac_rfn_view(geoac_ctx* ctx, GeoacRfnView* v);
 extern "C" void geoac_rfn_release(void* state);                                  // geoac_destroy: frees the refinement state (device current, stream idle)
-// geoac_stations.hip: device copy of the stations [n_sta][2] of the current lists (GEOAC_E_INVALID without current lists)
-extern "C" int  geoac_sta_coords_dev(geoac_ctx* ctx, const double** sta_dev, int* n_sta);
 
 #endif

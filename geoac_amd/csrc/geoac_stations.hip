@@ -28,7 +28,9 @@
 #include <vector>
 
 #include "../../include/geoac_stations.h"
+#include "geoac_launch_int.h"
 #include "geoac_stations_int.h"
+#include "geoac_tri_rule.h"
 
 #pragma clang fp contract(off)
 
@@ -75,15 +77,7 @@ __global__ void k_sta_prep(StaDev D){
     }
 }
 
-struct Tri { double w0, w1, w2, s; bool hit; };
-
-__device__ inline double wrap180(double d){ return d - 360.0 * floor((d + 180.0) / 360.0); }
-__device__ inline double cross2(double ax, double ay, double bx, double by){ return ax * by - ay * bx; }
-__device__ inline double len2(double ax, double ay, double bx, double by){ const double dx = bx - ax, dy = by - ay; return dx * dx + dy * dy; }
-__device__ inline double dmax(double a, double b){ return a > b ? a : b; }
-__device__ inline double dmin(double a, double b){ return a < b ? a : b; }
-
-// the triangle of three landing-table corners against a station: filters, cross products, sign rule
+// the triangle of three landing-table corners against a station: the filters on the corners, then the rule of geoac_tri_rule.h
 __device__ inline Tri tri_test(const StaDev& D, const double4& c0, const double4& c1, const double4& c2, double s0, double s1){
     Tri T;
     T.w0 = T.w1 = T.w2 = T.s = 0.0; T.hit = false;
@@ -93,14 +87,7 @@ __device__ inline Tri tri_test(const StaDev& D, const double4& c0, const double4
     const double x0 = c0.x - s0, x1 = c1.x - s0, x2 = c2.x - s0;
     double y0 = c0.y - s1, y1 = c1.y - s1, y2 = c2.y - s1;
     if(D.spherical){ y0 = wrap180(y0); y1 = wrap180(y1); y2 = wrap180(y2); }
-    const double e2 = dmax(dmax(len2(x0, y0, x1, y1), len2(x1, y1, x2, y2)), len2(x2, y2, x0, y0));
-    if(!(e2 <= D.edge2)) return T;
-    T.w0 = cross2(x1, y1, x2, y2);
-    T.w1 = cross2(x2, y2, x0, y0);
-    T.w2 = cross2(x0, y0, x1, y1);
-    T.s = (T.w0 + T.w1) + T.w2;
-    T.hit = T.s != 0.0 && ((T.w0 >= 0.0 && T.w1 >= 0.0 && T.w2 >= 0.0) || (T.w0 <= 0.0 && T.w1 <= 0.0 && T.w2 <= 0.0));
-    return T;
+    return tri_rule(x0, y0, x1, y1, x2, y2, D.edge2);
 }
 
 // ray indices of the corners a, b, c, d of a cell
@@ -111,7 +98,6 @@ __device__ inline void cell_rays(const StaDev& D, int cell, int* a, int* b, int*
     *a = j * D.n_theta + i; *b = *a + 1; *d = jn * D.n_theta + i; *c = *d + 1;
 }
 
-__device__ inline double interp(double W0, double W1, double W2, double v0, double v1, double v2){ return ((W0 * v0) + (W1 * v1)) + (W2 * v2); }
 __device__ inline double near(double v0, double vk){ return v0 + wrap180(vk - v0); }
 
 // the row of a hit; r0, r1, r2 the ray indices of its corners
@@ -246,28 +232,11 @@ struct StaState {
     unsigned long long sta_gen = 0, land_gen = 0;         // the context's invalidation counter they were made at (0: never)
     std::vector<double> h_axes;                           // host copy of what `axes` is filled from (alive while the copy runs)
     int M = 0, F = 0, n_sta = 0, cap = 0;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair ev;
     size_t rows_bytes() const { return sizeof(double) * (size_t)M * n_sta * cap * GEOAC_STA_STRIDE; }
     size_t level_bytes() const { return sizeof(double) * (size_t)M * n_sta * cap * F; }
     size_t hits_bytes() const { return sizeof(uint32_t) * (size_t)M * n_sta; }
 };
-
-unsigned blocks_for(long long n, int per_block){
-    long long b = (n + per_block - 1) / per_block;
-    if(b < 1) b = 1;
-    if(b > (1ll << 20)) b = 1ll << 20;
-    return (unsigned)b;
-}
-
-int grow(void** p, size_t* cap, size_t need){
-    if(*p && *cap >= need) return GEOAC_OK;
-    if(*p){ hipFree(*p); *p = nullptr; *cap = 0; }                  // (hipFree waits for the work that may still read it)
-    if(hipMalloc(p, need ? need : 8) != hipSuccess){ (void)hipGetLastError(); *p = nullptr; return GEOAC_E_NOMEM; }
-    *cap = need;
-    return GEOAC_OK;
-}
-
-bool spherical(int eqset){ return eqset == GEOAC_EQ_GLOBAL || eqset == GEOAC_EQ_GLOBAL_RNGDEP; }
 
 // the first thing wrong with a spec, or NULL; *code the status it earns
 const char* spec_fault(int eqset, const geoac_station_spec* s, int n_rays, int n_sta, int* code){
@@ -291,19 +260,14 @@ const char* spec_fault(int eqset, const geoac_station_spec* s, int n_rays, int n
 
 bool same_bits(double a, double b){ uint64_t x, y; memcpy(&x, &a, 8); memcpy(&y, &b, 8); return x == y; }
 
-struct Bound { geoac_ctx* ctx; GeoacStaView v; StaState* st; };
+struct Bound { geoac_ctx* ctx; GeoacLaunchView v; StaState* st; };
 
 int bind(geoac_ctx* ctx, const char* what, bool create, Bound* b){
-    if(!ctx) return GEOAC_E_INVALID;
-    b->ctx = ctx;
-    int rc = geoac_sta_view(ctx, &b->v);
+    int rc = bind_launch(ctx, what, GEOAC_SLOT_STA, &b->v);
     if(rc) return rc;
-    if(!b->v.map.fresh)
-        return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": no completed launch, or new angles, an atmosphere upload, geoac_set_sources or "
-                                                     "geoac_set_frequencies have come since it (launch again)").c_str());
+    b->ctx = ctx;
     if(!*b->v.state && create) *b->v.state = new StaState();
     b->st = (StaState*)*b->v.state;
-    if(hipSetDevice(b->v.map.device) != hipSuccess) return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": hipSetDevice failed").c_str());
     return GEOAC_OK;
 }
 
@@ -316,11 +280,6 @@ int bind_lists(geoac_ctx* ctx, const char* what, Bound* b){
     return GEOAC_OK;
 }
 
-int hip_fail(geoac_ctx* ctx, const char* what, hipError_t e){
-    return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define STACHK(what, call) do { hipError_t e_ = (call); if(e_ != hipSuccess) return hip_fail(b.ctx, what, e_); } while(0)
-
 }  // namespace
 
 extern "C" void geoac_sta_release(void* state){
@@ -330,14 +289,50 @@ extern "C" void geoac_sta_release(void* state){
     if(st->axes) hipFree(st->axes);
     if(st->cnt) hipFree(st->cnt);
     if(st->out) hipFree(st->out);
-    if(st->e0) hipEventDestroy(st->e0);
-    if(st->e1) hipEventDestroy(st->e1);
+    st->ev.release();
     delete st;
 }
 
 extern "C" const char* geoac_station_fault(int eqset, const geoac_station_spec* spec, int n_rays, int n_sta){
     int code;
     return spec_fault(eqset, spec, n_rays, n_sta, &code);
+}
+
+std::string geoac_lattice_fault(const GeoacLaunchView& v, int nt, int np){
+    if(v.n_ang != v.map.n_rays || !v.theta_deg || !v.phi_deg) return "the context holds no launch angles for the records";
+    for(int j = 0; j < np; j++)
+        for(int i = 0; i < nt; i++)
+            if(!same_bits(v.theta_deg[(size_t)j * nt + i], v.theta_deg[i]) || !same_bits(v.phi_deg[(size_t)j * nt + i], v.phi_deg[(size_t)j * nt]))
+                return "the launch angles are not an n_theta x n_phi lattice (ray " + std::to_string((size_t)j * nt + i) +
+                       " differs from its row's theta or its column's phi; ray = j * n_theta + i, the order of geoac_fan_enumerate)";
+    return std::string();
+}
+
+void geoac_lattice_extent(int leg_min, int leg_max, int legs, int nt, int np, int phi_periodic, int* leg0, int* n_legs, int* n_cells){
+    const int leg_last = leg_max < legs - 1 ? leg_max : legs - 1;
+    *leg0 = leg_min;
+    *n_legs = leg_last >= leg_min ? leg_last - leg_min + 1 : 0;
+    *n_cells = (nt - 1) * (phi_periodic ? np : np - 1);
+}
+
+extern "C" int geoac_sta_land_dev(geoac_ctx* ctx, const char* what, const void** land_dev){
+    Bound b;
+    int rc = bind(ctx, what, true, &b);
+    if(rc) return rc;
+    StaState* st = b.st; const GeoacMapView& v = b.v.map;
+    if(st->land_gen != v.gen){
+        const size_t n_land = (size_t)v.M * v.legs * v.n_rays;
+        if(grow(&st->land, &st->land_cap, sizeof(double4) * n_land))
+            return geoac_map_fail(ctx, GEOAC_E_NOMEM, (std::string(what) + ": no device memory for the landing table (" + std::to_string((sizeof(double4) * n_land) >> 20) + " MiB)").c_str());
+        StaDev D{};
+        D.rec = v.rec; D.land = (double4*)st->land; D.spherical = spherical(v.eqset) ? 1 : 0;
+        D.M = v.M; D.n_rays = v.n_rays; D.legs = v.legs;
+        hipLaunchKernelGGL(k_sta_prep, dim3(blocks_for((long long)n_land, 256)), dim3(256), 0, (hipStream_t)v.stream, D);
+        GEOAC_CHK(what, hipGetLastError());
+        st->land_gen = v.gen;
+    }
+    if(land_dev) *land_dev = st->land;
+    return GEOAC_OK;
 }
 
 extern "C" int geoac_station_check(int eqset, const geoac_station_spec* spec, int n_rays, int n_sta){
@@ -355,19 +350,15 @@ extern "C" int geoac_fan_stations(geoac_ctx* ctx, const geoac_station_spec* spec
     if(const char* fault = spec_fault(v.eqset, spec, v.n_rays, n_sta, &code)) return geoac_map_fail(ctx, code, (std::string("fan_stations: ") + fault).c_str());
     if(!sta) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_stations: sta is NULL");
     const int nt = spec->n_theta, np = spec->n_phi;
-    if(b.v.n_ang != v.n_rays || !b.v.theta_deg || !b.v.phi_deg) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_stations: the context holds no launch angles for the records");
-    for(int j = 0; j < np; j++)
-        for(int i = 0; i < nt; i++)
-            if(!same_bits(b.v.theta_deg[(size_t)j * nt + i], b.v.theta_deg[i]) || !same_bits(b.v.phi_deg[(size_t)j * nt + i], b.v.phi_deg[(size_t)j * nt]))
-                return geoac_map_fail(ctx, GEOAC_E_INVALID, ("fan_stations: the launch angles are not an n_theta x n_phi lattice (ray " + std::to_string((size_t)j * nt + i) +
-                                                             " differs from its row's theta or its column's phi; ray = j * n_theta + i, the order of geoac_fan_enumerate)").c_str());
+    const std::string lattice = geoac_lattice_fault(b.v, nt, np);
+    if(!lattice.empty()) return geoac_map_fail(ctx, GEOAC_E_INVALID, ("fan_stations: " + lattice).c_str());
     StaState* st = b.st;
     hipStream_t s = (hipStream_t)v.stream;
     st->sta_gen = 0;                                   // (no current lists until these are complete)
-    if(!st->e0){ STACHK(what, hipEventCreate(&st->e0)); STACHK(what, hipEventCreate(&st->e1)); }
-    STACHK(what, hipEventRecord(st->e0, s));
-    void* level = nullptr; size_t level_bytes = 0;
+    GEOAC_CHK(what, st->ev.start(s));
+    void* level = nullptr; size_t level_bytes = 0; const void* land = nullptr;
     if((rc = geoac_fan_level_dev(ctx, &level, &level_bytes))) return rc;         // (formed on first use after a launch, geoac_map.hip)
+    if((rc = geoac_sta_land_dev(ctx, what, &land))) return rc;                   // (the same, below)
     st->M = v.M; st->F = v.F; st->n_sta = n_sta; st->cap = spec->cap;
 
     StaDev D{};
@@ -375,42 +366,34 @@ extern "C" int geoac_fan_stations(geoac_ctx* ctx, const geoac_station_spec* spec
     D.turn_tol = spec->turn_tol; D.edge2 = spec->edge_max * spec->edge_max;
     D.spherical = spherical(v.eqset) ? 1 : 0; D.periodic = spec->phi_periodic;
     D.M = v.M; D.F = v.F; D.n_rays = v.n_rays; D.legs = v.legs; D.n_theta = nt; D.n_phi = np; D.n_sta = n_sta; D.cap = spec->cap;
-    D.leg0 = spec->leg_min;
-    const int leg_last = spec->leg_max < v.legs - 1 ? spec->leg_max : v.legs - 1;
-    D.n_legs = leg_last >= D.leg0 ? leg_last - D.leg0 + 1 : 0;
-    D.n_cells = (nt - 1) * (spec->phi_periodic ? np : np - 1);
+    geoac_lattice_extent(spec->leg_min, spec->leg_max, v.legs, nt, np, spec->phi_periodic, &D.leg0, &D.n_legs, &D.n_cells);
     D.n_chunks = (D.n_cells + STA_CHUNK - 1) / STA_CHUNK;
     D.nseg = D.n_legs * D.n_chunks;
     const long long n_lists = (long long)v.M * n_sta, n_seg_all = n_lists * D.nseg;
 
-    const size_t n_land = (size_t)v.M * v.legs * v.n_rays, n_axes = (size_t)nt + np + 2 * (size_t)n_sta;
+    const size_t n_axes = (size_t)nt + np + 2 * (size_t)n_sta;
     const size_t out_need = st->rows_bytes() + st->level_bytes() + st->hits_bytes();
-    if(grow(&st->land, &st->land_cap, sizeof(double4) * n_land) || grow(&st->axes, &st->axes_cap, sizeof(double) * n_axes) ||
+    if(grow(&st->axes, &st->axes_cap, sizeof(double) * n_axes) ||
        grow(&st->cnt, &st->cnt_cap, sizeof(unsigned) * (size_t)n_seg_all) || grow(&st->out, &st->out_cap, out_need))
         return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_stations: no device memory for the lists (" + std::to_string(out_need >> 20) + " MiB for " + std::to_string(v.M) + " members x " +
                                                    std::to_string(n_sta) + " stations x " + std::to_string(spec->cap) + " rows)").c_str());
     // lattice axes and stations: one host block, one copy (the block lives in the state until the next call)
-    STACHK(what, hipStreamSynchronize(s));             // (an earlier call's copy may still read h_axes)
+    GEOAC_CHK(what, hipStreamSynchronize(s));             // (an earlier call's copy may still read h_axes)
     st->h_axes.resize(n_axes);
     for(int i = 0; i < nt; i++) st->h_axes[i] = b.v.theta_deg[i];
     for(int j = 0; j < np; j++) st->h_axes[nt + j] = b.v.phi_deg[(size_t)j * nt];
     for(size_t k = 0; k < 2 * (size_t)n_sta; k++) st->h_axes[nt + np + k] = sta[k];
-    STACHK(what, hipMemcpyAsync(st->axes, st->h_axes.data(), sizeof(double) * n_axes, hipMemcpyHostToDevice, s));
+    GEOAC_CHK(what, hipMemcpyAsync(st->axes, st->h_axes.data(), sizeof(double) * n_axes, hipMemcpyHostToDevice, s));
     D.theta_ax = (const double*)st->axes; D.phi_ax = D.theta_ax + nt; D.sta = D.phi_ax + np;
-    D.land = (double4*)st->land; D.cnt = (unsigned*)st->cnt;
+    D.land = (double4*)land; D.cnt = (unsigned*)st->cnt;
     D.rows = (double*)st->out; D.lvl = (double*)((char*)st->out + st->rows_bytes()); D.hits = (unsigned*)((char*)st->out + st->rows_bytes() + st->level_bytes());
-    STACHK(what, hipMemsetAsync(st->out, 0, out_need, s));
-    if(st->land_gen != v.gen){
-        hipLaunchKernelGGL(k_sta_prep, dim3(blocks_for((long long)n_land, 256)), dim3(256), 0, s, D);
-        STACHK(what, hipGetLastError());
-        st->land_gen = v.gen;
-    }
+    GEOAC_CHK(what, hipMemsetAsync(st->out, 0, out_need, s));
     if(n_seg_all > 0){
         hipLaunchKernelGGL(k_sta_count, dim3(blocks_for(n_seg_all, 4)), dim3(256), 0, s, D, n_seg_all);
         hipLaunchKernelGGL(k_sta_rows, dim3(blocks_for(n_seg_all, 4)), dim3(256), 0, s, D, n_seg_all);
-        STACHK(what, hipGetLastError());
+        GEOAC_CHK(what, hipGetLastError());
     }
-    STACHK(what, hipEventRecord(st->e1, s));
+    GEOAC_CHK(what, st->ev.stop(s));
     st->sta_gen = v.gen;
     return GEOAC_OK;
 }
@@ -426,7 +409,7 @@ extern "C" int geoac_fan_stations_shape(geoac_ctx* ctx, int* n_members, int* n_f
     return GEOAC_OK;
 }
 
-// for geoac_refine.hip (geoac_refine_int.h): the stations of the current lists as the kernels read them (the tail of `axes`)
+// for geoac_refine.hip: the stations of the current lists as the kernels read them (the tail of `axes`)
 extern "C" int geoac_sta_coords_dev(geoac_ctx* ctx, const double** sta_dev, int* n_sta){
     Bound b;
     int rc = bind_lists(ctx, "fan_refine", &b);
@@ -456,10 +439,10 @@ extern "C" int geoac_fan_stations_fetch(geoac_ctx* ctx, uint32_t* hits, double* 
     const StaState* st = b.st;
     hipStream_t s = (hipStream_t)b.v.map.stream;
     const char* base = (const char*)st->out;
-    if(rows) STACHK(what, hipMemcpyAsync(rows, base, st->rows_bytes(), hipMemcpyDeviceToHost, s));
-    if(level) STACHK(what, hipMemcpyAsync(level, base + st->rows_bytes(), st->level_bytes(), hipMemcpyDeviceToHost, s));
-    if(hits) STACHK(what, hipMemcpyAsync(hits, base + st->rows_bytes() + st->level_bytes(), st->hits_bytes(), hipMemcpyDeviceToHost, s));
-    STACHK(what, hipStreamSynchronize(s));
+    if(rows) GEOAC_CHK(what, hipMemcpyAsync(rows, base, st->rows_bytes(), hipMemcpyDeviceToHost, s));
+    if(level) GEOAC_CHK(what, hipMemcpyAsync(level, base + st->rows_bytes(), st->level_bytes(), hipMemcpyDeviceToHost, s));
+    if(hits) GEOAC_CHK(what, hipMemcpyAsync(hits, base + st->rows_bytes() + st->level_bytes(), st->hits_bytes(), hipMemcpyDeviceToHost, s));
+    GEOAC_CHK(what, hipStreamSynchronize(s));
     return GEOAC_OK;
 }
 
@@ -469,9 +452,6 @@ extern "C" int geoac_fan_stations_timing(geoac_ctx* ctx, double* ms){
     int rc = bind_lists(ctx, what, &b);
     if(rc) return rc;
     if(!ms) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_stations_timing: NULL argument");
-    STACHK(what, hipEventSynchronize(b.st->e1));
-    float t = 0;
-    STACHK(what, hipEventElapsedTime(&t, b.st->e0, b.st->e1));
-    *ms = t;
+    GEOAC_CHK(what, b.st->ev.ms(ms));
     return GEOAC_OK;
 }

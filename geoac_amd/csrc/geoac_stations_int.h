@@ -1,20 +1,24 @@
 // geoac_stations_int.h - the seam between geoac_api.cpp (which owns geoac_ctx) and geoac_stations.hip (station arrivals,
-// include/geoac_stations.h): the map's view of the last completed launch (geoac_map_int.h), the caller's launch angles as the context keeps
-// them on the host (ray order, not the slot order of the device arrays), and one pointer slot for the station state.
+// include/geoac_stations.h), and what geoac_stations.hip owns for the other post-launch files: the landing table of a launch, the proof that
+// the launch angles are a lattice, and the stations of the current lists.
 #ifndef GEOAC_STATIONS_INT_H_
 #define GEOAC_STATIONS_INT_H_
 
+#include <string>
+
 #include "geoac_map_int.h"
 
-struct GeoacStaView {
-    GeoacMapView map;              // (its `state` is the map's slot: not used here)
-    const double* theta_deg;       // [n_ang] host, the angles of geoac_fan_set_angles
-    const double* phi_deg;
-    int n_ang;
-    void** state;                  // slot in the context for the station state (NULL until the first use)
-};
-
-extern "C" int  geoac_sta_view(geoac_ctx* ctx, GeoacStaView* v);
 extern "C" void geoac_sta_release(void* state);                                  // geoac_destroy: frees the station state (device current, stream idle)
+
+// device copy of the stations [n_sta][2] of the current lists (GEOAC_E_INVALID without current lists)
+extern "C" int  geoac_sta_coords_dev(geoac_ctx* ctx, const double** sta_dev, int* n_sta);
+// the landing table of the last completed launch, land[M][legs][n_rays] of double4 (c0, c1, turn, valid) in the map's coordinates: formed on
+// first use after a launch (the station state is created if the context has none) and kept until the next.  `what` names the caller in messages.
+extern "C" int  geoac_sta_land_dev(geoac_ctx* ctx, const char* what, const void** land_dev);
+
+// why the launch angles of the view are not an n_theta x n_phi lattice bit for bit (ray = j * n_theta + i), or an empty string
+std::string geoac_lattice_fault(const GeoacLaunchView& v, int n_theta, int n_phi);
+// what of a lattice takes part: legs leg0 .. leg0 + n_legs - 1 of the launch's `legs`, and the number of lattice cells
+void geoac_lattice_extent(int leg_min, int leg_max, int legs, int n_theta, int n_phi, int phi_periodic, int* leg0, int* n_legs, int* n_cells);
 
 #endif

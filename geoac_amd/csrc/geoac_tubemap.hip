@@ -1,13 +1,11 @@
 // geoac_tubemap.hip - tube maps (include/geoac_tubemap.h): the landing triangles of the last completed launch rasterised on a regular grid,
 // on the device.
 //
-// Reads the record table, the level table of geoac_map.hip and the lattice axes of the launch angles; writes only buffers of its own.  No
-// kernel of the launch plan is involved.
+// Reads the record table, the level table of geoac_map.hip, the landing table of geoac_stations.hip (land[M][legs][n_rays] of (c0, c1, turn,
+// valid), 32 B per corner, in the map's coordinates) and the lattice axes of the launch angles; writes only buffers of its own.  No kernel of
+// the launch plan is involved.  The layers are a GeoacLayers of geoac_map.hip, which fills and finishes them; the tail holds the work counters.
 //
 // Kernels:
-//   k_tube_prep     landing table land[M][legs][n_rays] of (c0, c1, turn, valid), 32 B per corner, in the map's coordinates: the file's own
-//                   table, formed once per launch.
-//   k_tube_fill     initial values of all layers and of the work counters in one pass.
 //   k_tube_raster   <0>: one lane per (member, leg, lattice cell), the cell's two triangles one after the other.  A triangle that passes the
 //                   filters that do not depend on the cell centre proposes a box of centres: the bounding box of its corners in cell-index
 //                   space, widened by one cell on every side, clipped to the grid; on the spherical sets the longitudes are first brought within
@@ -17,14 +15,12 @@
 //                   boxes are balloted, and the wave takes them one at a time: corners and box broadcast, 64 centres per trip.  A hit adds 1
 //                   to COUNT and takes part in the key minima / maxima.
 //                   <1>: the same walk again; hits whose level equals their cell's LEVEL_MAX compete for BEST with leg * n_tri + tri.
-//   k_tube_finish   keys back to doubles in place, empty-cell markers.
-//   k_tube_detect   members with LEVEL_MAX >= detect_db.
 // Every reduction is an integer atomic (u64 add; u64 min / max on the order-preserving key of a double; u64 min on the hit's key), so the
 // layers do not depend on the order the hits are seen in.
 //
 // The arithmetic of the test and of the interpolated values is fixed by the headers and restated in tests/station_reference.py and
 // tests/tubemap_reference.py: every product is rounded before it is added, so this file is compiled with contraction off (the pragma below; the
-// Makefile gives the same flag).  The inline triangle functions restate those of geoac_stations.hip; that file is not touched.
+// Makefile gives the same flag).  The rule at a centre is that of geoac_tri_rule.h, which geoac_stations.hip uses at a station.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
@@ -34,28 +30,21 @@
 #include <string>
 
 #include "../../include/geoac_tubemap.h"
+#include "geoac_launch_int.h"
+#include "geoac_stations_int.h"
 #include "geoac_tubemap_int.h"
+#include "geoac_tri_rule.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 const double kTubePi = 3.141592653589793238462643;
-const unsigned long long kSign = 0x8000000000000000ull;
 const double kTubeSlack = 1.0 / 1099511627776.0;      // 2^-40: slack of the station-independent side test, relative to the coordinates' size
-
-// order-preserving key of a double, as in geoac_map.hip
-__device__ inline unsigned long long tube_key(double v){
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | kSign);
-}
-__device__ inline double tube_unkey(unsigned long long k){
-    return __longlong_as_double((long long)((k >> 63) ? (k & ~kSign) : ~k));
-}
 
 struct TubeDev {
     const double* rec; const double* level;       // the launch's tables
-    double4* land;                                // [M][legs][n_rays]: c0, c1, turn, valid
+    const double4* land;                          // [M][legs][n_rays]: c0, c1, turn, valid
     unsigned long long *count, *lvl, *stats;      // COUNT | TTIME_MIN | CEL_MAX follow one another, M * cells words each; LEVEL_MAX | BEST, M * F * cells each
     unsigned* detect;
     double o0, o1, s0, s1;                        // the grid
@@ -66,48 +55,6 @@ struct TubeDev {
     int leg0, n_legs, n_cells, coop_min;          // legs leg0 .. leg0 + n_legs - 1 take part; cells of the lattice
     long long cells;                              // n0 * n1
 };
-
-// one thread per (m, leg, ray): the landing point in the map's coordinates
-__global__ void k_tube_prep(TubeDev D){
-    const long long n = (long long)D.M * D.legs * D.n_rays;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for(long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride){
-        const int ray = (int)(t % D.n_rays);
-        const long long ml = t / D.n_rays;
-        const int leg = (int)(ml % D.legs);
-        const long long m = ml / D.legs;
-        const double* R = D.rec + ((m * D.n_rays + ray) * D.legs + leg) * GEOAC_REC_STRIDE;
-        double4 o;
-        if(D.spherical){
-            o.x = R[GEOAC_REC_STATE + 1] * 180.0 / kTubePi;
-            o.y = R[GEOAC_REC_STATE + 2] * 180.0 / kTubePi;
-        } else {
-            o.x = R[GEOAC_REC_STATE + 0];
-            o.y = R[GEOAC_REC_STATE + 1];
-        }
-        o.z = R[GEOAC_REC_TURN];
-        o.w = R[GEOAC_REC_VALID];
-        D.land[t] = o;
-    }
-}
-
-// initial values of the layers, back to back in one allocation: COUNT 0 | TTIME key ~0 | CEL key 0 | LEVEL key 0 | BEST max | stats 0 | DETECT 0
-__global__ void k_tube_fill(unsigned long long* w, long long n_mc, long long n_mfc, long long n_words){
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for(long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_words; i += stride){
-        unsigned long long v = 0;
-        if(i >= n_mc && i < 2 * n_mc) v = ~0ull;
-        else if(i >= 3 * n_mc + n_mfc && i < 3 * n_mc + 2 * n_mfc) v = 0x7fffffffffffffffull;
-        w[i] = v;
-    }
-}
-
-__device__ inline double wrap180(double d){ return d - 360.0 * floor((d + 180.0) / 360.0); }
-__device__ inline double cross2(double ax, double ay, double bx, double by){ return ax * by - ay * bx; }
-__device__ inline double len2(double ax, double ay, double bx, double by){ const double dx = bx - ax, dy = by - ay; return dx * dx + dy * dy; }
-__device__ inline double dmax(double a, double b){ return a > b ? a : b; }
-__device__ inline double dmin(double a, double b){ return a < b ? a : b; }
-__device__ inline double interp(double W0, double W1, double W2, double v0, double v1, double v2){ return ((W0 * v0) + (W1 * v1)) + (W2 * v2); }
 
 // a triangle on its way through the walk: the landing points and turning heights of its corners, where its records are, and its box
 struct TubeTri {
@@ -183,12 +130,9 @@ __device__ inline void tube_test(const TubeDev& D, const TubeTri& T, int i0, int
     const double x0 = T.x0 - s0, x1 = T.x1 - s0, x2 = T.x2 - s0;
     double y0 = T.y0 - s1, y1 = T.y1 - s1, y2 = T.y2 - s1;
     if(D.spherical){ y0 = wrap180(y0); y1 = wrap180(y1); y2 = wrap180(y2); }
-    const double e2 = dmax(dmax(len2(x0, y0, x1, y1), len2(x1, y1, x2, y2)), len2(x2, y2, x0, y0));
-    if(!(e2 <= D.edge2)) return;
-    const double w0 = cross2(x1, y1, x2, y2), w1 = cross2(x2, y2, x0, y0), w2 = cross2(x0, y0, x1, y1);
-    const double s = (w0 + w1) + w2;
-    if(!(s != 0.0 && ((w0 >= 0.0 && w1 >= 0.0 && w2 >= 0.0) || (w0 <= 0.0 && w1 <= 0.0 && w2 <= 0.0)))) return;
-    const double W0 = w0 / s, W1 = w1 / s, W2 = w2 / s;
+    const Tri R = tri_rule(x0, y0, x1, y1, x2, y2, D.edge2);
+    if(!R.hit) return;
+    const double W0 = R.w0 / R.s, W1 = R.w1 / R.s, W2 = R.w2 / R.s;
     const double turn = interp(W0, W1, W2, T.t0, T.t1, T.t2);
     if(!(turn >= D.turn_min && turn < D.turn_max)) return;
     const long long per_m = (long long)D.n_rays * D.legs;
@@ -203,8 +147,8 @@ __device__ inline void tube_test(const TubeDev& D, const TubeTri& T, int i0, int
         const long long b = (long long)T.m * D.cells + cell;
         const long long mc = (long long)D.M * D.cells;
         atomicAdd(&D.count[b], 1ull);
-        atomicMin(&D.count[mc + b], tube_key(tt));
-        atomicMax(&D.count[2 * mc + b], tube_key(rg / tt));
+        atomicMin(&D.count[mc + b], geoac_key(tt));
+        atomicMax(&D.count[2 * mc + b], geoac_key(rg / tt));
     }
     const unsigned long long key = (unsigned long long)((long long)T.leg * (2ll * D.n_cells) + T.tri);
     for(int f = 0; f < D.F; f++){
@@ -212,8 +156,8 @@ __device__ inline void tube_test(const TubeDev& D, const TubeTri& T, int i0, int
         const double lv = interp(W0, W1, W2, L[q0], L[q1], L[q2]);
         if(!isfinite(lv)) continue;
         const long long b = ((long long)T.m * D.F + f) * D.cells + cell;
-        if(PASS == 0) atomicMax(&D.lvl[b], tube_key(lv));
-        else if(D.lvl[b] == tube_key(lv)) atomicMin(&D.lvl[(long long)D.M * D.F * D.cells + b], key);
+        if(PASS == 0) atomicMax(&D.lvl[b], geoac_key(lv));
+        else if(D.lvl[b] == geoac_key(lv)) atomicMin(&D.lvl[(long long)D.M * D.F * D.cells + b], key);
     }
 }
 
@@ -309,68 +253,18 @@ __global__ void __launch_bounds__(64) k_tube_raster(const TubeDev* __restrict__ 
     }
 }
 
-// one thread per (m, f, cell): keys back to doubles in place, empty-cell markers
-__global__ void k_tube_finish(TubeDev D){
-    const long long n = D.cells * D.M * D.F;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    unsigned long long* ttime = D.count + D.cells * D.M; unsigned long long* cel = ttime + D.cells * D.M; unsigned long long* best = D.lvl + n;
-    const unsigned long long p_inf = 0x7ff0000000000000ull, m_inf = 0xfff0000000000000ull;
-    for(long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride){
-        const unsigned long long k = D.lvl[i];
-        if(k == 0ull){ D.lvl[i] = m_inf; best[i] = ~0ull; }
-        else D.lvl[i] = (unsigned long long)__double_as_longlong(tube_unkey(k));
-        const long long c = i % D.cells, mf = i / D.cells;
-        if(mf % D.F == 0){
-            const long long b = (mf / D.F) * D.cells + c;
-            const bool any = D.count[b] != 0ull;
-            ttime[b] = any ? (unsigned long long)__double_as_longlong(tube_unkey(ttime[b])) : p_inf;
-            cel[b] = any ? (unsigned long long)__double_as_longlong(tube_unkey(cel[b])) : m_inf;
-        }
-    }
-}
-
-// one thread per (f, cell): members whose LEVEL_MAX reaches detect_db
-__global__ void k_tube_detect(TubeDev D){
-    const long long n = D.cells * D.F;
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for(long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride){
-        const long long c = i % D.cells, f = i / D.cells;
-        unsigned hits = 0;
-        for(int m = 0; m < D.M; m++){
-            const double lv = __longlong_as_double((long long)D.lvl[((long long)m * D.F + f) * D.cells + c]);
-            hits += lv >= D.detect_db ? 1u : 0u;
-        }
-        D.detect[i] = hits;
-    }
-}
-
 static_assert(sizeof(TubeDev) <= 512, "TubeState::args holds one TubeDev");
 
+static_assert(GEOAC_TUBE_COUNT == GEOAC_MAP_COUNT && GEOAC_TUBE_TTIME_MIN == GEOAC_MAP_TTIME_MIN && GEOAC_TUBE_CEL_MAX == GEOAC_MAP_CEL_MAX &&
+              GEOAC_TUBE_LEVEL_MAX == GEOAC_MAP_LEVEL_MAX && GEOAC_TUBE_BEST == GEOAC_MAP_BEST && GEOAC_TUBE_LAYERS == GEOAC_MAP_LAYERS, "GeoacLayers numbers the layers as geoac_map.h does");
+
 struct TubeState {
-    void* layers = nullptr; size_t layers_cap = 0;
-    void* land = nullptr; size_t land_cap = 0;
+    GeoacLayers L{};                                      // tail: the four work counters
     void* args = nullptr; size_t args_cap = 0;           // the walk's arguments (k_tube_args)
-    unsigned long long tube_gen = 0, land_gen = 0;        // the context's invalidation counter they were made at (0: never)
+    unsigned long long tube_gen = 0;                      // the context's invalidation counter the map was made at (0: never)
     geoac_tube_spec spec{};
-    int M = 0, F = 0;
-    long long cells = 0;
-    bool detect = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    size_t mc() const { return (size_t)M * (size_t)cells; }
-    size_t mfc() const { return mc() * (size_t)F; }
+    EventPair ev;
 };
-
-unsigned blocks_for(long long n, long long cap){ long long b = (n + 255) / 256; if(b < 1) b = 1; if(b > cap) b = cap; return (unsigned)b; }
-
-int grow(void** p, size_t* cap, size_t need){
-    if(*p && *cap >= need) return GEOAC_OK;
-    if(*p){ hipFree(*p); *p = nullptr; *cap = 0; }                  // (hipFree waits for the work that may still read it)
-    if(hipMalloc(p, need ? need : 8) != hipSuccess){ (void)hipGetLastError(); *p = nullptr; return GEOAC_E_NOMEM; }
-    *cap = need;
-    return GEOAC_OK;
-}
-
-bool spherical(int eqset){ return eqset == GEOAC_EQ_GLOBAL || eqset == GEOAC_EQ_GLOBAL_RNGDEP; }
 
 // the first thing wrong with a spec, or NULL; *code the status it earns
 const char* spec_fault(int eqset, const geoac_tube_spec* s, int n_rays, int* code){
@@ -381,16 +275,7 @@ const char* spec_fault(int eqset, const geoac_tube_spec* s, int n_rays, int* cod
         return "not implemented for the 2-D set: a fan on one axis has no landing triangles (geoac_fan_map bins its arrivals)";
     }
     if(!s) return "spec is NULL";
-    // the grid and the bands, as geoac_map_check has them
-    for(int a = 0; a < 2; a++){
-        if(!std::isfinite(s->origin[a])) return "origin must be finite";
-        if(!std::isfinite(s->step[a]) || !(s->step[a] > 0.0)) return "step must be finite and greater than 0";
-        if(s->n[a] < 1) return "n must be at least 1 per axis";
-    }
-    if((long long)s->n[0] * s->n[1] > (long long)GEOAC_MAP_MAX_CELLS) return "n[0] * n[1] exceeds GEOAC_MAP_MAX_CELLS (2^24)";
-    if(s->wrap_lon != 0 && s->wrap_lon != 1) return "wrap_lon must be 0 or 1";
-    if(s->wrap_lon && !spherical(eqset)) return "wrap_lon is for the spherical sets only (a Cartesian set has no longitude)";
-    if(std::isnan(s->turn_min) || std::isnan(s->turn_max) || !(s->turn_min < s->turn_max)) return "turning-height band: need turn_min < turn_max, neither NaN (-inf / +inf: no bound)";
+    if(const char* f = geoac_grid_fault(eqset, s->origin, s->step, s->n, s->wrap_lon, s->turn_min, s->turn_max)) return f;
     // the lattice and the triangle filters: geoac_station_check's own verdict on the shared fields
     geoac_station_spec st;
     st.n_theta = s->n_theta; st.n_phi = s->n_phi; st.phi_periodic = s->phi_periodic; st.leg_min = s->leg_min; st.leg_max = s->leg_max;
@@ -406,21 +291,14 @@ const char* spec_fault(int eqset, const geoac_tube_spec* s, int n_rays, int* cod
     return nullptr;
 }
 
-bool same_bits(double a, double b){ uint64_t x, y; memcpy(&x, &a, 8); memcpy(&y, &b, 8); return x == y; }
-
-struct Bound { geoac_ctx* ctx; GeoacTubeView v; TubeState* st; };
+struct Bound { geoac_ctx* ctx; GeoacLaunchView v; TubeState* st; };
 
 int bind(geoac_ctx* ctx, const char* what, bool create, Bound* b){
-    if(!ctx) return GEOAC_E_INVALID;
-    b->ctx = ctx;
-    int rc = geoac_tube_view(ctx, &b->v);
+    int rc = bind_launch(ctx, what, GEOAC_SLOT_TUBE, &b->v);
     if(rc) return rc;
-    if(!b->v.map.fresh)
-        return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": no completed launch, or new angles, an atmosphere upload, geoac_set_sources or "
-                                                     "geoac_set_frequencies have come since it (launch again)").c_str());
+    b->ctx = ctx;
     if(!*b->v.state && create) *b->v.state = new TubeState();
     b->st = (TubeState*)*b->v.state;
-    if(hipSetDevice(b->v.map.device) != hipSuccess) return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": hipSetDevice failed").c_str());
     return GEOAC_OK;
 }
 
@@ -433,42 +311,14 @@ int bind_map(geoac_ctx* ctx, const char* what, Bound* b){
     return GEOAC_OK;
 }
 
-int hip_fail(geoac_ctx* ctx, const char* what, hipError_t e){
-    return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": " + hipGetErrorString(e)).c_str());
-}
-#define TUBECHK(what, call) do { hipError_t e_ = (call); if(e_ != hipSuccess) return hip_fail(b.ctx, what, e_); } while(0)
-
-// byte offset and size of a layer inside the allocation
-void layer_span(const TubeState* st, int layer, size_t* off, size_t* bytes){
-    const size_t mc = st->mc() * 8, mfc = st->mfc() * 8;
-    switch(layer){
-    case GEOAC_TUBE_COUNT:     *off = 0;            *bytes = mc;  break;
-    case GEOAC_TUBE_TTIME_MIN: *off = mc;           *bytes = mc;  break;
-    case GEOAC_TUBE_CEL_MAX:   *off = 2 * mc;       *bytes = mc;  break;
-    case GEOAC_TUBE_LEVEL_MAX: *off = 3 * mc;       *bytes = mfc; break;
-    default:                   *off = 3 * mc + mfc; *bytes = mfc; break;
-    }
-}
-size_t stats_off(const TubeState* st){ return 3 * st->mc() * 8 + 2 * st->mfc() * 8; }
-size_t detect_off(const TubeState* st){ return stats_off(st) + 4 * 8; }
-size_t detect_bytes(const TubeState* st){ return (size_t)st->F * (size_t)st->cells * 4; }
-
-int fetch(Bound& b, const char* what, void* host, size_t off, size_t bytes){
-    TUBECHK(what, hipMemcpyAsync(host, (const char*)b.st->layers + off, bytes, hipMemcpyDeviceToHost, (hipStream_t)b.v.map.stream));
-    TUBECHK(what, hipStreamSynchronize((hipStream_t)b.v.map.stream));
-    return GEOAC_OK;
-}
-
 }  // namespace
 
 extern "C" void geoac_tube_release(void* state){
     TubeState* st = (TubeState*)state;
     if(!st) return;
-    if(st->layers) hipFree(st->layers);
-    if(st->land) hipFree(st->land);
+    if(st->L.base) hipFree(st->L.base);
     if(st->args) hipFree(st->args);
-    if(st->e0) hipEventDestroy(st->e0);
-    if(st->e1) hipEventDestroy(st->e1);
+    st->ev.release();
     delete st;
 }
 
@@ -493,69 +343,54 @@ extern "C" int geoac_fan_tubemap(geoac_ctx* ctx, const geoac_tube_spec* spec){
     int code;
     if(const char* fault = spec_fault(v.eqset, spec, v.n_rays, &code)) return geoac_map_fail(ctx, code, (std::string("fan_tubemap: ") + fault).c_str());
     const int nt = spec->n_theta, np = spec->n_phi;
-    if(b.v.n_ang != v.n_rays || !b.v.theta_deg || !b.v.phi_deg) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap: the context holds no launch angles for the records");
-    for(int j = 0; j < np; j++)
-        for(int i = 0; i < nt; i++)
-            if(!same_bits(b.v.theta_deg[(size_t)j * nt + i], b.v.theta_deg[i]) || !same_bits(b.v.phi_deg[(size_t)j * nt + i], b.v.phi_deg[(size_t)j * nt]))
-                return geoac_map_fail(ctx, GEOAC_E_INVALID, ("fan_tubemap: the launch angles are not an n_theta x n_phi lattice (ray " + std::to_string((size_t)j * nt + i) +
-                                                             " differs from its row's theta or its column's phi; ray = j * n_theta + i, the order of geoac_fan_enumerate)").c_str());
+    const std::string lattice = geoac_lattice_fault(b.v, nt, np);
+    if(!lattice.empty()) return geoac_map_fail(ctx, GEOAC_E_INVALID, ("fan_tubemap: " + lattice).c_str());
     TubeState* st = b.st;
     hipStream_t s = (hipStream_t)v.stream;
     st->tube_gen = 0;                                  // (no current tube map until this one is complete)
-    if(!st->e0){ TUBECHK(what, hipEventCreate(&st->e0)); TUBECHK(what, hipEventCreate(&st->e1)); }
-    TUBECHK(what, hipEventRecord(st->e0, s));
-    void* level = nullptr; size_t level_bytes = 0;
+    GEOAC_CHK(what, st->ev.start(s));
+    void* level = nullptr; size_t level_bytes = 0; const void* land = nullptr;
     if((rc = geoac_fan_level_dev(ctx, &level, &level_bytes))) return rc;         // (formed on first use after a launch, geoac_map.hip)
-    st->spec = *spec; st->M = v.M; st->F = v.F;
-    st->cells = (long long)spec->n[0] * spec->n[1];
-    st->detect = !std::isnan(spec->detect_db);
-    const size_t n_land = (size_t)v.M * v.legs * v.n_rays;
-    const size_t need = detect_off(st) + ((detect_bytes(st) + 7) & ~(size_t)7);
-    if(grow(&st->layers, &st->layers_cap, need) || grow(&st->land, &st->land_cap, sizeof(double4) * n_land) || grow(&st->args, &st->args_cap, 512))
-        return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_tubemap: no device memory for the layers (" + std::to_string(need >> 20) + " MiB for " + std::to_string(v.M) + " members x " +
-                                                   std::to_string(v.F) + " frequencies x " + std::to_string(st->cells) + " cells)").c_str());
+    if((rc = geoac_sta_land_dev(ctx, what, &land))) return rc;                   // (the same, geoac_stations.hip)
+    st->spec = *spec;
+    GeoacLayers& L = st->L;
+    L.M = v.M; L.F = v.F; L.cells = (long long)spec->n[0] * spec->n[1]; L.tail_words = 4; L.detect = !std::isnan(spec->detect_db);
+    if(geoac_layers_grow(&L) || grow(&st->args, &st->args_cap, 512))
+        return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_tubemap: no device memory for the layers (" + std::to_string(geoac_layers_bytes(&L) >> 20) + " MiB for " + std::to_string(v.M) + " members x " +
+                                                   std::to_string(v.F) + " frequencies x " + std::to_string(L.cells) + " cells)").c_str());
     TubeDev D{};
-    D.rec = v.rec; D.level = (const double*)level; D.land = (double4*)st->land;
-    char* base = (char*)st->layers;
+    D.rec = v.rec; D.level = (const double*)level; D.land = (const double4*)land;
+    char* base = (char*)L.base;
     size_t off, bytes;
-    layer_span(st, GEOAC_TUBE_COUNT, &off, &bytes);     D.count = (unsigned long long*)(base + off);
-    layer_span(st, GEOAC_TUBE_LEVEL_MAX, &off, &bytes); D.lvl = (unsigned long long*)(base + off);
-    D.stats = (unsigned long long*)(base + stats_off(st));
-    D.detect = (unsigned*)(base + detect_off(st));
+    geoac_layers_span(&L, GEOAC_TUBE_COUNT, &off, &bytes);     D.count = (unsigned long long*)(base + off);
+    geoac_layers_span(&L, GEOAC_TUBE_LEVEL_MAX, &off, &bytes); D.lvl = (unsigned long long*)(base + off);
+    geoac_layers_tail_span(&L, &off, &bytes);                  D.stats = (unsigned long long*)(base + off);
+    geoac_layers_detect_span(&L, &off, &bytes);                D.detect = (unsigned*)(base + off);
     D.o0 = spec->origin[0]; D.o1 = spec->origin[1]; D.s0 = spec->step[0]; D.s1 = spec->step[1]; D.n0 = spec->n[0]; D.n1 = spec->n[1];
-    D.turn_tol = spec->turn_tol; D.edge2 = spec->edge_max * spec->edge_max; 
+    D.turn_tol = spec->turn_tol; D.edge2 = spec->edge_max * spec->edge_max;
     const double mag = (fabs(spec->origin[0]) + spec->n[0] * spec->step[0]) + (fabs(spec->origin[1]) + spec->n[1] * spec->step[1]) + (spherical(v.eqset) ? 720.0 : 0.0);
     const double pre = 2.0 * spec->edge_max + kTubeSlack * (mag + spec->edge_max);
     D.pre2 = pre * pre;
     D.turn_min = spec->turn_min; D.turn_max = spec->turn_max; D.detect_db = spec->detect_db;
     D.spherical = spherical(v.eqset) ? 1 : 0;
     D.M = v.M; D.F = v.F; D.n_rays = v.n_rays; D.legs = v.legs; D.n_theta = nt; D.n_phi = np;
-    D.leg0 = spec->leg_min;
-    const int leg_last = spec->leg_max < v.legs - 1 ? spec->leg_max : v.legs - 1;
-    D.n_legs = leg_last >= D.leg0 ? leg_last - D.leg0 + 1 : 0;
-    D.n_cells = (nt - 1) * (spec->phi_periodic ? np : np - 1);
-    D.cells = st->cells;
+    geoac_lattice_extent(spec->leg_min, spec->leg_max, v.legs, nt, np, spec->phi_periodic, &D.leg0, &D.n_legs, &D.n_cells);
+    D.cells = L.cells;
     // GEOAC_TUBE_COOP (diagnostic, tools/perf_tubemap.py): another threshold for the cooperative walk; the layers do not depend on it
     D.coop_min = GEOAC_TUBE_COOP_MIN;
     if(const char* e = getenv("GEOAC_TUBE_COOP")){ const long t = strtol(e, nullptr, 10); if(t >= 0 && t <= 0x7fffffffl) D.coop_min = (int)t; }
     const long long n_items = (long long)v.M * D.n_legs * D.n_cells;
-    const long long n_mc = (long long)st->mc(), n_mfc = (long long)st->mfc(), n_words = (long long)(need / 8);
-    if(st->land_gen != v.gen){
-        hipLaunchKernelGGL(k_tube_prep, dim3(blocks_for((long long)n_land, 1ll << 20)), dim3(256), 0, s, D);
-        TUBECHK(what, hipGetLastError());
-        st->land_gen = v.gen;
-    }
-    hipLaunchKernelGGL(k_tube_fill, dim3(blocks_for(n_words, 1ll << 20)), dim3(256), 0, s, (unsigned long long*)st->layers, n_mc, n_mfc, n_words);
+    geoac_layers_fill(&L, s);
     if(n_items > 0){
-        const unsigned n_blk = blocks_for(n_items * 4, 1ll << 18);       // (one wave of 64 items per block)
+        const unsigned n_blk = blocks_for(n_items * 4, 256, 1ll << 18);  // (one wave of 64 items per block)
         hipLaunchKernelGGL(k_tube_args, dim3(1), dim3(64), 0, s, D, (TubeDev*)st->args);
         hipLaunchKernelGGL(k_tube_raster<0>, dim3(n_blk), dim3(64), 0, s, (const TubeDev*)st->args, n_items);
         hipLaunchKernelGGL(k_tube_raster<1>, dim3(n_blk), dim3(64), 0, s, (const TubeDev*)st->args, n_items);
     }
-    hipLaunchKernelGGL(k_tube_finish, dim3(blocks_for(n_mfc, 1ll << 20)), dim3(256), 0, s, D);
-    if(st->detect) hipLaunchKernelGGL(k_tube_detect, dim3(blocks_for(st->cells * v.F, 1ll << 20)), dim3(256), 0, s, D);
-    TUBECHK(what, hipGetLastError());
-    TUBECHK(what, hipEventRecord(st->e1, s));
+    geoac_layers_finish(&L, s);
+    if(L.detect) geoac_layers_detect(&L, spec->detect_db, s);
+    GEOAC_CHK(what, hipGetLastError());
+    GEOAC_CHK(what, st->ev.stop(s));
     st->tube_gen = v.gen;
     return GEOAC_OK;
 }
@@ -564,8 +399,8 @@ extern "C" int geoac_fan_tubemap_shape(geoac_ctx* ctx, int* n_members, int* n_fr
     Bound b;
     int rc = bind_map(ctx, "fan_tubemap_shape", &b);
     if(rc) return rc;
-    if(n_members) *n_members = b.st->M;
-    if(n_freq) *n_freq = b.st->F;
+    if(n_members) *n_members = b.st->L.M;
+    if(n_freq) *n_freq = b.st->L.F;
     if(n0) *n0 = b.st->spec.n[0];
     if(n1) *n1 = b.st->spec.n[1];
     return GEOAC_OK;
@@ -574,40 +409,25 @@ extern "C" int geoac_fan_tubemap_shape(geoac_ctx* ctx, int* n_members, int* n_fr
 extern "C" int geoac_fan_tubemap_dev(geoac_ctx* ctx, int layer, void** dev_ptr, size_t* bytes){
     Bound b;
     int rc = bind_map(ctx, "fan_tubemap_dev", &b);
-    if(rc) return rc;
-    if(layer < 0 || layer >= GEOAC_TUBE_LAYERS) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap_dev: unknown layer");
-    size_t off, n;
-    layer_span(b.st, layer, &off, &n);
-    if(dev_ptr) *dev_ptr = (char*)b.st->layers + off;
-    if(bytes) *bytes = n;
-    return GEOAC_OK;
+    return rc ? rc : geoac_layers_dev(ctx, "fan_tubemap_dev", &b.st->L, layer, dev_ptr, bytes);
 }
 
 extern "C" int geoac_fan_tubemap_fetch(geoac_ctx* ctx, int layer, void* host){
     Bound b;
     int rc = bind_map(ctx, "fan_tubemap_fetch", &b);
-    if(rc) return rc;
-    if(layer < 0 || layer >= GEOAC_TUBE_LAYERS || !host) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap_fetch: unknown layer / NULL buffer");
-    size_t off, n;
-    layer_span(b.st, layer, &off, &n);
-    return fetch(b, "fan_tubemap_fetch", host, off, n);
+    return rc ? rc : geoac_layers_fetch(ctx, "fan_tubemap_fetch", &b.st->L, b.v.map.stream, layer, host);
 }
 
 extern "C" int geoac_fan_tubemap_fetch_detect(geoac_ctx* ctx, uint32_t* detect_host){
     Bound b;
     int rc = bind_map(ctx, "fan_tubemap_fetch_detect", &b);
-    if(rc) return rc;
-    if(!detect_host) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap_fetch_detect: NULL buffer");
-    if(!b.st->detect) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap_fetch_detect: the tube map was made without a detection threshold (detect_db = NaN)");
-    return fetch(b, "fan_tubemap_fetch_detect", detect_host, detect_off(b.st), detect_bytes(b.st));
+    return rc ? rc : geoac_layers_fetch_detect(ctx, "fan_tubemap_fetch_detect", "tube map", &b.st->L, b.v.map.stream, detect_host);
 }
 
 extern "C" int geoac_fan_tubemap_stats(geoac_ctx* ctx, uint64_t* stats4){
     Bound b;
     int rc = bind_map(ctx, "fan_tubemap_stats", &b);
-    if(rc) return rc;
-    if(!stats4) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap_stats: NULL buffer");
-    return fetch(b, "fan_tubemap_stats", stats4, stats_off(b.st), 4 * 8);
+    return rc ? rc : geoac_layers_fetch_tail(ctx, "fan_tubemap_stats", &b.st->L, b.v.map.stream, stats4);
 }
 
 extern "C" int geoac_fan_tubemap_timing(geoac_ctx* ctx, double* ms){
@@ -615,9 +435,6 @@ extern "C" int geoac_fan_tubemap_timing(geoac_ctx* ctx, double* ms){
     int rc = bind_map(ctx, "fan_tubemap_timing", &b);
     if(rc) return rc;
     if(!ms) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_tubemap_timing: NULL argument");
-    TUBECHK("fan_tubemap_timing", hipEventSynchronize(b.st->e1));
-    float t = 0;
-    TUBECHK("fan_tubemap_timing", hipEventElapsedTime(&t, b.st->e0, b.st->e1));
-    *ms = t;
+    GEOAC_CHK("fan_tubemap_timing", b.st->ev.ms(ms));
     return GEOAC_OK;
 }

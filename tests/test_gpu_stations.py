@@ -13,6 +13,7 @@ import harness as H
 import map_cases as MC
 import station_cases as SC
 import station_reference as SR
+import tubemap_cases as TC
 import test_gpu_globalrd as TGG
 import test_gpu_rngdep as TGR
 from parity import compare_records, parse_eig_results, ring_golden_name, ring_receivers
@@ -42,10 +43,9 @@ def _lattice_of(case):
     return SC.lattice(**(SC.PARITY_LATTICE_RD if case["kind"] in ("3drd", "globalrd") else SC.PARITY_LATTICE))
 
 
-def _launch(G, case, tmpdir, params=None):
-    """the map case's launch over the lattice fan: context (left open), records [M][n_rays][legs][32], angles, lattice shape"""
+def _context(G, case, tmpdir, params=None):
+    """the map case's context (left open), set up and not launched"""
     eq, kind, prm = case["eq"], case["kind"], dict(case["params"], **(params or {}))
-    th, ph, nt, nph = _lattice_of(case)
     if kind in ("3drd", "globalrd"):
         ctx = (TGR if kind == "3drd" else TGG)._ctx(MC.write_grid(kind, str(tmpdir)), **prm)
     else:
@@ -59,6 +59,13 @@ def _launch(G, case, tmpdir, params=None):
             ctx.set_sources(SOURCES[eq][:case["n_src"]])
         if kind == "freqs":
             ctx.set_frequencies(case["freqs"])
+    return ctx
+
+
+def _launch(G, case, tmpdir, params=None):
+    """the map case's launch over the lattice fan: context (left open), records [M][n_rays][legs][32], angles, lattice shape"""
+    ctx = _context(G, case, tmpdir, params)
+    th, ph, nt, nph = _lattice_of(case)
     rec, _ = ctx.run(th, ph)
     return ctx, rec.reshape((-1,) + rec.shape[-3:]), th, ph, nt, nph
 
@@ -144,6 +151,12 @@ def test_repeated_calls_leave_the_launch_alone(G):
     assert steps2 == steps and ctx.timing()["epochs"] == epochs
     assert np.array_equal(SR.bits(after), SR.bits(before))
     assert ctx.stations_timing() > 0.0
+    # the landing table is shared with tubemap(): a smaller lattice, either module asking first, then the 13 x 9 launch again
+    (hits, _, _), small = TC.small_lattice_step(ctx, lambda: _context(G, case, None), "stations")
+    print(f"7 x 5 lattice, {hits.shape[0]} members: station hits {hits.sum(axis=0).tolist()}, hits on the grid {int(small['count'].sum())}")
+    SR.assert_lists_equal(ctx.stations(sta=sta, n_theta=nt, n_phi=nph, cap=6), first)
+    after, steps2 = ctx.fetch()
+    assert steps2 == steps and np.array_equal(SR.bits(after), SR.bits(before))      # (the same launch again: the same records)
     ctx.close()
 
 

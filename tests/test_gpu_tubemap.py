@@ -176,6 +176,18 @@ def test_repeated_calls_invalidation_and_refusals(G):
     with pytest.raises(G.GeoAcError, match="invalid.*not an n_theta x n_phi lattice"):
         ctx.tubemap(**dict(sp, n_theta=nph, n_phi=nt))
     TR.assert_layers_equal(ctx.tubemap(**sp), want, "after the refusals")
+
+    # the landing table is shared with stations(): a smaller lattice, either module asking first, then the 13 x 9 launch again
+    def make_ctx():
+        c = G.FanContext(H.EQ_GLOBAL, device=0)
+        _upload(c, [_toy(H.EQ_GLOBAL)])
+        c.set_params(**L["params"])
+        return c
+
+    (hits, _, _), small = TC.small_lattice_step(ctx, make_ctx, "tubemap")
+    print(f"7 x 5 lattice: hits on the grid {int(small['count'].sum())}, station hits {hits[0].tolist()}")
+    assert small["count"].sum() > 0 and (hits > 0).any()                            # (tests/test_tubemap_host.py: so it is on the oracle's records)
+    TR.assert_layers_equal(ctx.tubemap(**sp), want, "after the small lattice")
     ctx.close()
     c2 = G.FanContext(H.EQ_2D, device=0)
     _upload(c2, [_toy(H.EQ_2D)])

@@ -153,7 +153,7 @@ def test_map_kernels_use_no_scratch():
         subprocess.check_call(["make", "-s", "-j", "4", "-C", os.path.join(ROOT, "geoac_amd", "csrc"), "ARCH=gfx950"])
     rows, cur = [], None
     for line in open(path):
-        m = re.search(r"remark: .*?(Function Name|VGPRs Spill|ScratchSize \[bytes/lane\]): (\S+)", line)
+        m = re.search(r"remark: .*?(Function Name|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
         if m.group(1) == "Function Name":
@@ -163,9 +163,13 @@ def test_map_kernels_use_no_scratch():
             cur[m.group(1).split(" [")[0]] = int(m.group(2))
     names = {n for r in rows for n in re.findall(r"k_map_[a-z]+", r["name"])}
     assert names == {"k_map_fill", "k_map_level", "k_map_bin", "k_map_best", "k_map_finish", "k_map_detect"}, names
+    shared = [r for r in rows if re.search(r"k_map_(fill|finish|detect)", r["name"])]     # the layers' kernels, which the tube map runs as well
+    assert len(shared) == 3, [r["name"] for r in shared]
     for r in rows:
-        assert "ScratchSize" in r and "VGPRs Spill" in r, r
+        assert "ScratchSize" in r and "VGPRs Spill" in r and "SGPRs Spill" in r and "LDS Size" in r, r
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, r
+    for r in shared:
+        assert r["SGPRs Spill"] == 0 and r["LDS Size"] == 0, r
 
 
 @pytest.mark.parametrize("name", sorted(MC.CASES))

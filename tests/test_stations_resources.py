@@ -14,7 +14,7 @@ def test_station_kernels_use_no_scratch():
         subprocess.check_call(["make", "-s", "-j", "4", "-C", os.path.join(ROOT, "geoac_amd", "csrc"), "ARCH=gfx950"])
     rows, cur = [], None
     for line in open(REPORT):
-        m = re.search(r"remark: .*?(Function Name|VGPRs Spill|ScratchSize \[bytes/lane\]): (\S+)", line)
+        m = re.search(r"remark: .*?(Function Name|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\S+)", line)
         if not m:
             continue
         if m.group(1) == "Function Name":
@@ -27,3 +27,5 @@ def test_station_kernels_use_no_scratch():
     assert all("ScratchSize" in r for r in rows)
     offenders = [f'{r["name"]}: {r["ScratchSize"]} B/lane scratch, {r.get("VGPRs Spill", 0)} spilled VGPRs' for r in rows if r["ScratchSize"] != 0 or r.get("VGPRs Spill", 0) != 0]
     assert not offenders, "\n".join(offenders)
+    prep = [r for r in rows if "k_sta_prep" in r["name"]]                          # the landing table's kernel, which serves the tube map as well
+    assert len(prep) == 1 and prep[0]["SGPRs Spill"] == 0 and prep[0]["LDS Size"] == 0, prep

@@ -165,3 +165,17 @@ def test_grid_literals_meet_the_conditions_on_the_oracle(name):
     if case.get("cooperative"):
         # cells several times smaller than the landing triangles: the reached cells outnumber the triangles of both legs several times over
         assert int((ref["count"][0] >= 1).sum()) >= 3 * 2 * 2 * (nt - 1) * (nph - 1)
+
+
+def test_small_lattice_literals_on_the_oracle():
+    """the small-lattice step of the repeated-call GPU tests (tests/tubemap_cases.py small_lattice_step) is not vacuous: on the CPU oracle's records
+    of the 7 x 5 fan the reference tube map on SMALL_GRID has hits, and so has at least one of the five stations"""
+    rec, level, th, ph, nt, nph = TC.oracle_tables(dict(TC.LAUNCHES["global"], lattice=TC.SMALL_LATTICE), None)
+    assert (nt, nph) == (7, 5) and TC.SMALL_GRID["n"] == (6, 7)
+    sp = TR.spec(n_theta=nt, n_phi=nph, **TC.SMALL_GRID)
+    G.tube_check(H.EQ_GLOBAL, G.tube_spec(**sp), th.size)
+    ref = TR.reference_tubemap(H.EQ_GLOBAL, rec, th, ph, level, sp)
+    hits = SR.reference_stations(H.EQ_GLOBAL, rec, th, ph, level, SR.spec(n_theta=nt, n_phi=nph, edge_max=TC.SMALL_GRID["edge_max"], cap=TC.SMALL_CAP), TC.SMALL_STATIONS)[0]
+    print("7 x 5 fan: hits on the grid", int(ref["count"].sum()), "cells reached", int((ref["count"] > 0).sum()), "station hits", hits[0].tolist())
+    assert len(TC.SMALL_STATIONS) == 5 and ref["count"].sum() > 0 and (hits > 0).any()
+    assert int(hits.max()) <= TC.SMALL_CAP

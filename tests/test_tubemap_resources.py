@@ -24,7 +24,7 @@ def test_tube_map_kernels_use_no_scratch_no_spills_no_lds():
         elif cur is not None:
             cur[m.group(1).split(" [")[0]] = int(m.group(2))
     names = {n for r in rows for n in re.findall(r"k_tube_[a-z]+", r["name"])}
-    assert names == {"k_tube_prep", "k_tube_fill", "k_tube_args", "k_tube_raster", "k_tube_finish", "k_tube_detect"}, names
+    assert names == {"k_tube_args", "k_tube_raster"}, names                        # (the layers' kernels: geoac_map.hip; the landing table's: geoac_stations.hip)
     assert sum("k_tube_raster" in r["name"] for r in rows) == 2                     # the reducing walk and the BEST walk
     assert all(k in r for r in rows for k in ("ScratchSize", "VGPRs Spill", "SGPRs Spill", "LDS Size"))
     offenders = [f'{r["name"]}: {r["ScratchSize"]} B/lane scratch, {r["VGPRs Spill"]} + {r["SGPRs Spill"]} spilled VGPRs + SGPRs, {r["LDS Size"]} B LDS' for r in rows

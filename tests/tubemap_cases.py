@@ -43,6 +43,13 @@ GRID_FINE = dict(origin=(28.0, -6.0), step=(0.0625, 0.0625), n=(32, 48), edge_ma
 GRID_COARSE = dict(origin=(25.5, -11.5), step=(1.5, 1.5), n=(6, 7), edge_max=3.0)                       # cells larger than most triangles
 GRID_HALF_OFF = dict(origin=(28.0, -5.5), step=(0.25, 0.25), n=(24, 24), edge_max=3.0)                  # the landing area ends inside the grid
 
+# the small-lattice step of the repeated-call tests (small_lattice_step below): every second inclination and azimuth of SC.PARITY_LATTICE, 7 x 5;
+# edge_max doubled for the doubled triangles; five stations inside the westward fan's landing area
+SMALL_LATTICE = dict(theta_min=3.0, theta_max=39.0, theta_step=6.0, phi_min=-122.0, phi_max=-58.0, phi_step=16.0)
+SMALL_GRID = dict(GRID_COARSE, edge_max=6.0)
+SMALL_STATIONS = np.array([[30.0, -4.0], [30.5, -5.5], [29.0, -8.0], [31.5, -9.0], [28.5, -3.5]])
+SMALL_CAP = 8
+
 CASES = {
     "3d": dict(launch="3d", spec=dict(GRID_3D, detect_db=MC.DETECT_AMP)),
     "global": dict(launch="global", spec=dict(GRID_GLOBAL, detect_db=MC.DETECT_AMP)),
@@ -114,3 +121,53 @@ def oracle_tables(launch, tmpdir):
     if atten is None:
         atten = rec[0, :, :, H.REC["ATTEN"]][None]
     return rec, MR.level_numpy(rec, atten, prm["calc_amp"]), th, ph, nt, nph
+
+
+def stations_and_tubemap(ctx, nt, nph, tube_first):
+    """the station lists at SMALL_STATIONS and the tube map on SMALL_GRID of the context's launch, in either order: (hits, rows, level), layers"""
+    def lists():
+        return ctx.stations(sta=SMALL_STATIONS, n_theta=nt, n_phi=nph, edge_max=SMALL_GRID["edge_max"], cap=SMALL_CAP)
+
+    def layers():
+        return ctx.tubemap(**TR.spec(n_theta=nt, n_phi=nph, **SMALL_GRID))
+
+    if tube_first:
+        m = layers()
+        return lists(), m
+    return lists(), layers()
+
+
+def small_lattice_step(ctx, make_ctx, what=""):
+    """The landing table is one table per context, formed by whichever of stations() and tubemap() asks first after a launch (geoac_stations.hip).
+    `ctx` holds a completed 13 x 9 launch of SC.PARITY_LATTICE; make_ctx() gives a context set up alike with no launch.  After a 7 x 5 launch on
+    `ctx` (a table larger than its launch) the lists and layers are the same bits whichever module asks first - on `ctx` the stations, on a second
+    context that saw the same two launches the tube map - and equal those of a context that only ever saw the 7 x 5 launch.  Then the 13 x 9
+    launch again: on `ctx` (a stale table) and on the 7 x 5 context (a regrown table, the tube map asking first) the first results come back.
+    Returns the 7 x 5 results."""
+    import station_reference as SR
+
+    def same(got, want, why):
+        SR.assert_lists_equal(got[0], want[0])
+        TR.assert_layers_equal(got[1], want[1], what + " " + why)
+
+    th, ph, nt, nph = SC.lattice(**SC.PARITY_LATTICE)
+    ths, phs, nts, nphs = SC.lattice(**SMALL_LATTICE)
+    assert (nts, nphs) == (7, 5)
+    assert np.array_equal(ths.reshape(nphs, nts), th.reshape(nph, nt)[::2, ::2]) and np.array_equal(phs.reshape(nphs, nts), ph.reshape(nph, nt)[::2, ::2])
+    second, fresh = make_ctx(), make_ctx()
+    first = stations_and_tubemap(ctx, nt, nph, tube_first=False)
+    second.run(th, ph)
+    same(stations_and_tubemap(second, nt, nph, tube_first=True), first, "13 x 9, the tube map first")
+    for c in (ctx, second, fresh):
+        c.run(ths, phs)
+    small = stations_and_tubemap(ctx, nts, nphs, tube_first=False)
+    same(stations_and_tubemap(second, nts, nphs, tube_first=True), small, "7 x 5, the tube map first")
+    same(stations_and_tubemap(fresh, nts, nphs, tube_first=False), small, "7 x 5 on a context that saw nothing else")
+    assert small[1]["count"].shape != first[1]["count"].shape or not np.array_equal(small[1]["count"], first[1]["count"])      # (another launch, other layers)
+    ctx.run(th, ph)
+    same(stations_and_tubemap(ctx, nt, nph, tube_first=False), first, "13 x 9 again")
+    fresh.run(th, ph)
+    same(stations_and_tubemap(fresh, nt, nph, tube_first=True), first, "13 x 9 after 7 x 5, the tube map first")
+    second.close()
+    fresh.close()
+    return small
