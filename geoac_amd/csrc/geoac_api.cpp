@@ -187,6 +187,8 @@ struct geoac_ctx {
     bool trace_epochs = false;                    // GEOAC_TRACE_EPOCHS=1: per-epoch live counts on stderr
     bool no_gate = false;                         // GEOAC_NO_GATE=1: post-pass not held back behind the next RK4 launch (A/B measurements)
     bool no_pair = false;                         // GEOAC_NO_PAIR=1: force one lane per ray (A/B measurements)
+    bool range_skip = true;                       // RANGE_SKIP=0: range_skip2 = -1, every row of the spherical stratified set takes the full tests (EqGlobal::checks_fast; tests)
+    bool pole_fast = true;                        // POLE_FAST=0: pole_k = +inf, every step of that set runs with the pole guard (tests)
     bool grid_build_host = false;                 // GRID_BUILD=host: evaluation table of the grid sets by the host twin (geoac_grid_table_eq) instead of on the device
     int ev_slack = 72;                            // GEOAC_EV_SLACK: per-epoch event rows of a ray beyond its raypath samples (caustics); tests lower it to reach the overflow path
     int trio = 0;                                 // TRIO=1: slots that would take two lanes per ray run the wave-specialised kernel k_rk4_trio (the ray on one wave, one launch-angle system on each of two more)
@@ -309,10 +311,51 @@ int geoac_default_params(int eqset, geoac_params* p){
     return GEOAC_OK;
 }
 
+// The two constants of EqGlobal::checks_fast (k_rk4's step loop, spherical stratified set), and what they are derived from.  No context, no device: the
+// bounds are checked on the host (tests/test_gpu_step_votes.py).  out: range_thresh, range_skip2, pole_k, GEOAC_RCPC_EMAX, delta.
+//
+// range_skip2.  The range test fires when hav = sin^2(A / 2) + c sin^2(B / 2) > range_thresh = sin^2(limit / 2R), A = lat - lat_src, B = lon - lon_src,
+// c = cos(lat_src) cos(lat).  sin^2 x <= x^2, so hav <= (A^2 + |c| B^2) / 4 = q / 4 exactly in real arithmetic, and q < 4 range_thresh implies that the test
+// cannot fire.  In floating point the kernel's hav is within 3e-16 (absolute: it is formed from 1 - cos) of the real one and q within 1e-15 of itself; the
+// bound is therefore taken as 4 range_thresh (1 - 1e-9) - 1e-14, which covers both for every limit (the absolute part matters below ~1 km only; where
+// nothing is left of the bound every row takes the full test).  The degenerate limits as range_skip has them: a test that can never fire is never
+// prepared for (1e300), a limit <= 0 always is (-1).
+//
+// pole_k.  global_base forms 1 / cos(lat) of the stages 1-3 by a Newton step from stage 0's and needs its guard where e2 = 1 - cos(lat + d) / cos(lat)
+// exceeds GEOAC_RCPC_EMAX; d is the stage's latitude increment.  e2 = 1 - cos d + tan(lat) sin d, so |e2| <= |tan(lat)| |d| + d^2 / 2, plus 1e-15 for the
+// rounding of the carried sin / cos, of the stored reciprocal and of e2 itself.  |d| = a ds |dlat/ds| <= ds / r (the slope is a component of a unit vector
+// over r; a <= 1), ds <= ds_bound = max(min(0.05, ds_max), ds_min) (set_ds: 0.05 - 0.049 exp(..) <= 0.05 km, clamped to [ds_min, ds_max]), and r >= r_lo - ds_bound with r_lo = ground radius - 2 ds_bound: a row
+// lies above ground - ds (the row before it was not below the ground) and a stage at most ds below its row.  With delta = ds_bound / (r_lo - ds_bound)
+// (1 + 1e-12) every stage of a step from latitude lat has |e2| <= |tan(lat)| delta + delta^2 / 2 + 1e-15, and that is <= GEOAC_RCPC_EMAX when
+// |tan(lat)| <= t_max = (GEOAC_RCPC_EMAX - delta^2 / 2 - 1e-15) / delta.  pole_k = (1 + 1e-12) / t_max: a row with |sin(lat)| pole_k <= |cos(lat)| starts a
+// step whose guard is idle in every stage, so the step may run without it (51.9 degrees at ds_bound = 0.05 km, which is every ds_max >= 0.05).  No such latitude: +inf, every step guarded.
+extern "C" void geoac_probe_step_vote_consts(double range_limit, double r_earth, double ground_radius, double ds_min, double ds_max, double* out){
+    const double half = range_limit / (2.0 * r_earth);
+    double thresh, skip2;
+    if(half >= kPi / 2.0){ thresh = 2.0; skip2 = 1e300; }
+    else if(half <= 0.0){ thresh = -1.0; skip2 = -1.0; }
+    else {
+        const double s = sin(half);
+        thresh = s * s;
+        skip2 = 4.0 * thresh * (1.0 - 1e-9) - 1e-14;
+        if(!(skip2 > 0.0)) skip2 = -1.0;                     // (a limit of metres, or a NaN: every row takes the full test)
+    }
+    double pole_k = (double)INFINITY, delta = (double)INFINITY;
+    const double ds_top = ds_max < GEOAC_DS_TOP ? ds_max : GEOAC_DS_TOP;
+    const double dsb = ds_top > ds_min ? ds_top : ds_min;
+    const double r_lo = ground_radius - 2.0 * dsb;
+    if(dsb > 0.0 && r_lo - dsb > 0.0){
+        delta = dsb / (r_lo - dsb) * (1.0 + 1e-12);
+        const double t_max = (GEOAC_RCPC_EMAX - 0.5 * delta * delta - 1e-15) / delta;
+        if(t_max > 0.0) pole_k = (1.0 + 1e-12) / t_max;
+    }
+    out[0] = thresh; out[1] = skip2; out[2] = pole_k; out[3] = GEOAC_RCPC_EMAX; out[4] = delta;
+}
+
 // ---- launch-plan options (A/B measurements, tests; results never depend on them) ----
 static const char* const kOptionNames[] = {
     "S_ROWS", "NO_OVERLAP", "PP_BLOCKS", "ABS_TABLE", "ABS_TABLE_TOL", "PPFIX_CAP", "DUO", "TRIO", "EV_SLACK", "NO_PAIR", "PAIR_FRAC", "HYBRID_ROWS", "STAGGER_FRAC", "STAGGER_ROWS", "TWO_CHUNKS", "TRACE_EPOCHS", "NO_GATE", "SORT", "TILE", "PP_ONETRIP", "PP_LDS_TABLE", "PP_LDS_PAD", "CU_SPLIT", "CHUNK_GIB", "ACCUM_BATCH",
-    "NO_QUAD", "GRID_LANES", "OCT", "HEX", "SPREAD", "COMPACT", "QUAD_CACHE", "GRID_COOP", "SUB_EPOCHS", "SUB_MIN_WAVES", "SUB_TEST_STALL", "SMP_CAP", "GRID_BUILD", nullptr };
+    "NO_QUAD", "GRID_LANES", "OCT", "HEX", "SPREAD", "COMPACT", "QUAD_CACHE", "GRID_COOP", "SUB_EPOCHS", "SUB_MIN_WAVES", "SUB_TEST_STALL", "SMP_CAP", "GRID_BUILD", "RANGE_SKIP", "POLE_FAST", nullptr };
 const char* const* geoac_option_names(void){ return kOptionNames; }
 
 int geoac_set_option(geoac_ctx* ctx, const char* key, const char* value){
@@ -352,6 +395,8 @@ int geoac_set_option(geoac_ctx* ctx, const char* key, const char* value){
     else if(k == "STAGGER_ROWS"){ if(!dbl_ok || !(dv > 0.0 && dv <= 1.0)) return bad("a ratio in (0, 1]"); ctx->stagger_rows = dv; }
     else if(k == "HYBRID_ROWS"){ if(!dbl_ok || !(dv > 0.0 && dv <= 1.0)) return bad("a ratio in (0, 1]"); ctx->hybrid_rows = dv; }
     else if(k == "TWO_CHUNKS") return flag(ctx->two_chunks);
+    else if(k == "RANGE_SKIP") return flag(ctx->range_skip);
+    else if(k == "POLE_FAST") return flag(ctx->pole_fast);
     else if(k == "TRACE_EPOCHS") return flag(ctx->trace_epochs);
     else if(k == "NO_GATE") return flag(ctx->no_gate);
     else if(k == "SORT") return flag(ctx->sort_rays);
@@ -898,6 +943,10 @@ static int fan_launch_once(geoac_ctx* ctx){
         if(half >= kPi / 2.0){ P.range_thresh = 2.0; P.range_skip = 1e300; }      // asin saturates: the range test can never fire
         else if(half <= 0.0){ P.range_thresh = -1.0; P.range_skip = -1.0; }       // (always fires)
         else { double s = sin(half); P.range_thresh = s * s; P.range_skip = half * (1.0 - 1e-9); }
+        double c[5];
+        geoac_probe_step_vote_consts(p.range_limit, p.r_earth, P.ground, p.ds_min, p.ds_max, c);
+        P.range_skip2 = ctx->range_skip ? c[1] : -1.0;
+        P.pole_k = ctx->pole_fast ? c[2] : (double)INFINITY;
     }
     P.src[0] = p.src[0]; P.src[1] = p.src[1]; P.src[2] = p.src[2];
     P.freq = p.freq; P.tweak_abs = p.tweak_abs;

@@ -41,6 +41,10 @@
 #define GEOAC_LAT_OFF   1024    // lat_trig: entry of latitude 0
 #define GEOAC_LAT_N     2049    // ... entries (|lat| <= 8 rad; the index is clamped)
 #define GEOAC_PP_ROWS   16      // path segments per thread of k_postpass_tab (consecutive rows of one ray: each row is read once)
+#define GEOAC_DS_TOP    0.05    // km: the step size rule 0.05 - 0.049 exp(-h / 0.75) never exceeds it (set_ds; the host bounds a stage's latitude increment with it: pole_k)
+#ifndef GEOAC_RCPC_EMAX
+#define GEOAC_RCPC_EMAX 1.0e-5  // largest |1 - cos(lat) / cos(lat of stage 0)| the Newton step of the stage reciprocals is trusted with (global_base; its cube, 1e-15 - up to 9 ulp -, is the error left)
+#endif
 #define GEOAC_CNT_PPFLAG 28     // counters[+0]: entries of the fix-up list of the current k_postpass_tab launch; counters[+1]: path segments of the fan the absorption table did not serve (evaluated exactly by k_ppfix)
 
 // per-ray state slots (SoA rows of the state buffer)
@@ -94,6 +98,8 @@ struct GeoacDevParams {
     double  vert_limit, range_limit, range_thresh;   // range_thresh: sin^2(range_limit/(2 r_earth)) (Global)
     double  range_sq[2];            // 3-D stratified set: range_limit^2 (1 -/+ 1e-12): the horizontal range is compared squared outside this band (Eq3D::checks)
     double  range_skip;             // Global: while (|lat - lat_src| + |lon - lon_src|) / 2 stays below this, the range test cannot fire (EqGlobal::checks)
+    double  range_skip2;            // Global, step loop: while q = dlat^2 + |cos(lat_src) cos(lat)| dlon^2 stays below this, the range test cannot fire (EqGlobal::checks_fast; -1: never skipped)
+    double  pole_k;                 // Global, step loop: a row with |sin(lat)| pole_k <= |cos(lat)| starts a step whose stage reciprocals need no guard (EqGlobal::checks_fast; +inf: every step guarded)
     double  src[3];                 // as in geoac_params
     double  freq, tweak_abs;
     double  T_o, P_o;               // SuthBass reference temperature / pressure (ground), host-evaluated from the spline

@@ -38,9 +38,7 @@
 #ifndef GEOAC_RCPC
 #define GEOAC_RCPC 1                     // 1/r and 1/cos(lat) of stages 1-3 by a Newton step from stage 0's values (global_base); 0: a fresh seed per stage (A/B)
 #endif
-#ifndef GEOAC_RCPC_EMAX
-#define GEOAC_RCPC_EMAX 1.0e-5          // largest |1 - cos(lat) / cos(lat of stage 0)| the Newton step of GEOAC_RCPC is trusted with (its cube, 1e-15 - up to 9 ulp -, is the error left)
-#endif
+                                        // (GEOAC_RCPC_EMAX, the largest change of cos(lat) the Newton step is trusted with: geoac_device.h - the host derives pole_k from it)
 #ifndef GEOAC_AB
 #define GEOAC_AB 0                      // 1: A/B build (`make AB=1`) - also holds the diagnostic kernels the launch plan never selects
 #endif
@@ -346,10 +344,13 @@ struct GlobalStage { double n0, n1, n2, inm, cn, icg, dc, du, dv, v, cg2, ir, ic
 // Base ray: sources + right-hand side of r, lat, lon, nu_r, nu_t, nu_p (Global.cpp:222-272, 369-390).  S: the stage values the derivative
 // systems read (K2 only with AMP).
 struct NoHook { DEVINL void operator()() const {} };
+template <bool B> struct BoolC { static constexpr bool value = B; };     // a compile-time flag as a function argument (generic lambdas)
 // HOOK: called once the segment record has arrived (k_rk4_duo reads the consumed-message counter there, so that the answer is back
 // when the stage's message is published); ROT0: stage 0 of a step - the stage latitude IS the step's, no rotation (bit-identical to a rotation by 0)
 // LOCATED: rec already is the record of the stage's segment (seg_locate done by the caller: the skewed stage loop of k_rk4)
-template <bool AMP, int W, typename TabPtr, class HOOK = NoHook, bool ROT0 = false, bool LOCATED = false>
+// GUARD: the test on |e2| below.  false: only for steps that start on a row which passed the pole_k test of EqGlobal::checks_fast - there the guard
+// is provably idle (geoac_api.cpp, where pole_k is set), and leaving it out changes no bit; every other caller keeps it
+template <bool AMP, int W, typename TabPtr, class HOOK = NoHook, bool ROT0 = false, bool LOCATED = false, bool GUARD = true>
 DEVINL void global_base(TabPtr tab, const GeoacDevParams& P, int& seg, double* rec, const double* y, double sth0, double cth0, double dlat, double* dy, GlobalStage& S, const HOOK& hook = HOOK(), double* rcp0 = nullptr, bool first = false){
     const double r = y[0];
     const double n0 = y[3], n1 = y[4], n2 = y[5];
@@ -372,7 +373,7 @@ DEVINL void global_base(TabPtr tab, const GeoacDevParams& P, int& seg, double* r
         const double e1 = __builtin_fma(-r, rcp0[0], 1.0), e2 = __builtin_fma(-cth, rcp0[1], 1.0);
         ir = __builtin_fma(rcp0[0], __builtin_fma(e1, e1, e1), rcp0[0]);
         ico = __builtin_fma(rcp0[1], __builtin_fma(e2, e2, e2), rcp0[1]);
-        if(__builtin_expect(!(fabs(e2) <= GEOAC_RCPC_EMAX), 0)) ico = frcp(cth);
+        if(GUARD){ if(__builtin_expect(!(fabs(e2) <= GEOAC_RCPC_EMAX), 0)) ico = frcp(cth); }
     }
 #else
     const double ir  = frcp(r);
@@ -484,10 +485,10 @@ DEVINL void global_aux(const GlobalStage& S, const GlobalDerived& D, const doubl
 // (Measured and dropped, round 4: locating the NEXT stage's spline segment here, under the launch-angle systems - the abscissa r0 + w dy[0] is known once the base
 //  ray's slopes are - so that a dense fan of steep rays, where some lane of a wave changes segment in nearly every stage, finds its record in hand at the top of the
 //  next stage.  Same bits, but 40 instructions per step: config 3 355-357 -> 366-368 ms per pass, metric pass 117 -> 122 ms; profiles/r04_b_cfg3_ab.txt.)
-template <bool AMP, int NQ, bool ROT0 = false, typename TabPtr>
+template <bool AMP, int NQ, bool ROT0 = false, bool GUARD = true, typename TabPtr>
 DEVINL void global_rhs(TabPtr tab, const GeoacDevParams& P, int& seg, double* rec, const double* y, double sth0, double cth0, double dlat, double* dy, double* rcp0 = nullptr){
     GlobalStage S;
-    global_base<AMP, GEOAC_SEGW, TabPtr, NoHook, ROT0>(tab, P, seg, rec, y, sth0, cth0, dlat, dy, S, NoHook(), rcp0);
+    global_base<AMP, GEOAC_SEGW, TabPtr, NoHook, ROT0, false, GUARD>(tab, P, seg, rec, y, sth0, cth0, dlat, dy, S, NoHook(), rcp0);
     if(AMP){
         GlobalDerived D;
         global_derive(S, D);
@@ -874,11 +875,16 @@ template <bool AMP_> struct EqGlobal {
     static DEVINL void resume(const GeoacDevParams& P, RayCtx& C, const double* y){   // current row from the reference (kernel entry)
         rot_small(C.a[1], C.a[2], y[1] - C.a[0], C.cur[0], C.cur[1]);
     }
+    // GUARD = false: the step loop's steps from a row that passed the pole_k test (checks_fast)
+    template <bool GUARD, typename TabPtr>
+    static DEVINL void rhs_g(TabPtr tab, const GeoacDevParams& P, int& seg, const RayCtx& C, const double* y0, const double* yt, int stage, double* dy){
+        // (stage 0 - a constant where the step loop peels it: the stage latitude is the step's, no rotation)
+        if(stage == 0) global_rhs<AMP, 2, true, GUARD>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], 0.0, dy, C.rcp0);
+        else global_rhs<AMP, 2, false, GUARD>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], yt[1] - y0[1], dy, C.rcp0);
+    }
     template <typename TabPtr>
     static DEVINL void rhs(TabPtr tab, const GeoacDevParams& P, int& seg, const RayCtx& C, const double* y0, const double* yt, int stage, double* dy){
-        // (stage 0 - a constant where the step loop peels it: the stage latitude is the step's, no rotation)
-        if(stage == 0) global_rhs<AMP, 2, true>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], 0.0, dy, C.rcp0);
-        else global_rhs<AMP, 2>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], yt[1] - y0[1], dy, C.rcp0);
+        rhs_g<true>(tab, P, seg, C, y0, yt, stage, dy);
     }
     // GeoAc_BreakCheck / GeoAc_GroundCheck on the new row (Global.cpp:500-522)
     static DEVINL void checks(const GeoacDevParams& P, RayCtx& C, const double* y, const double* yn, int k, bool& brk, bool& gnd){
@@ -889,22 +895,53 @@ template <bool AMP_> struct EqGlobal {
         // haversine of the great-circle range: hav = sin^2(dlat/2) + cos(lat0) cos(lat) sin^2(dlon/2), with 2 sin^2(x/2) = 1 - cos x;
         // range = 2 R asin(sqrt(hav)) > limit  <=>  hav > sin^2(limit / 2R).
         // hav <= sin^2 a + sin^2 b <= sin^2(a + b) for a = |dlat| / 2, b = |dlon| / 2, a + b <= pi / 2 (the difference is 2 sin a sin b cos(a + b)):
-        // while a + b stays below limit / 2R (less 1e-9 of it: P.range_skip) the test cannot fire, and the ~50 instructions of the longitude
-        // rotation and the haversine are skipped by a wave whose rays are all that close to the source.  The longitude reference point goes
-        // stale meanwhile; the first row that is tested finds it further than GEOAC_ROT_MAX away and takes a new one.
+        // while a + b stays below limit / 2R (less 1e-9 of it: P.range_skip) the test cannot fire, and the longitude rotation and the haversine
+        // are skipped by a wave whose rays are all that close to the source.  (The block is 149 instructions in the two-lane kernel - 1135 per step
+        // with it against 986 without, tools/isa_mix.py --trace - and the branch is per lane: one lane beyond the bound switches it on for its wave.
+        // That is why k_rk4's step loop calls checks_fast instead, which sends a row to range_far only when the test could fire.)
+        // The longitude reference point goes stale meanwhile; the first row that is tested finds it further than GEOAC_ROT_MAX away and takes a new one.
         bool far = false;
-        if(fabs(yn[1] - P.src[1] * kPi / 180.0) * 0.5 + fabs(pl) * 0.5 >= P.range_skip){
-            const double dp = pl - C.a[3];
-            double tp0, tp1;
-            if(__builtin_expect(fabs(dp) > GEOAC_ROT_MAX, 0)){ C.a[3] = pl; fsincos(pl, C.a[4], C.a[5]); tp0 = C.a[4]; tp1 = C.a[5]; }
-            else rot_small(C.a[4], C.a[5], dp, tp0, tp1);
-            const double sl0 = P.src_trig[0], cl0 = P.src_trig[1];
-            double hav = __builtin_fma(cl0 * C.t[1], 0.5 * (1.0 - tp1), 0.5 * (1.0 - __builtin_fma(C.t[1], cl0, C.t[0] * sl0)));
-            far = hav > P.range_thresh;
-        }
+        if(fabs(yn[1] - P.src[1] * kPi / 180.0) * 0.5 + fabs(pl) * 0.5 >= P.range_skip) far = range_far(P, C, pl);
         brk = (yn[0] > P.vert_limit) || far;
         gnd = yn[0] < P.ground;
     }
+    // the range test itself: the longitude rotation and the haversine of the row whose sin / cos of latitude are in C.t; pl = lon - lon_src
+    static DEVINL bool range_far(const GeoacDevParams& P, RayCtx& C, double pl){
+        const double dp = pl - C.a[3];
+        double tp0, tp1;
+        if(__builtin_expect(fabs(dp) > GEOAC_ROT_MAX, 0)){ C.a[3] = pl; fsincos(pl, C.a[4], C.a[5]); tp0 = C.a[4]; tp1 = C.a[5]; }
+        else rot_small(C.a[4], C.a[5], dp, tp0, tp1);
+        const double sl0 = P.src_trig[0], cl0 = P.src_trig[1];
+        double hav = __builtin_fma(cl0 * C.t[1], 0.5 * (1.0 - tp1), 0.5 * (1.0 - __builtin_fma(C.t[1], cl0, C.t[0] * sl0)));
+        return hav > P.range_thresh;
+    }
+    // The tests of k_rk4's step loop: what EVERY row needs, and `slow` for the rows that need more - for those the wave votes itself out of the loop and the slow
+    // lanes run range_far on the same row (k_rk4).  In the loop stay: the carried sin / cos of the latitude (the statements of `checks`, the rare new reference
+    // point included), the vertical limit and the ground.  slow:
+    //  * the range test could fire: hav = sin^2(A / 2) + c sin^2(B / 2) <= (A^2 + |c| B^2) / 4 = q / 4 with A = lat - lat_src, B = lon - lon_src, c = cos(lat_src) cos(lat)
+    //    (sin^2 x <= x^2, whatever the sign of c: over a pole cos(lat) is negative), so hav <= range_thresh while q < range_skip2 (geoac_api.cpp: the margin there covers
+    //    the rounding of both sides).  Unlike range_skip's bound this one keeps the factor c of the longitude term and holds until the last ~0.25 % of the way to the limit (1500 km: q - 4 hav ~ q x^2 / 12 with x = limit / R);
+    //  * (POLE) the NEXT step, which starts on this row, could take the pole guard of global_base: only rows with |tan(lat)| <= 1 / pole_k start a step whose
+    //    stage reciprocals are formed without it (near_pole; geoac_api.cpp for the bound).
+    // !(.. <= ..), !(.. < ..): a NaN goes to the slow side.  For a lane that is not slow `checks` would return far = false: brk and gnd here are its answers.
+    // (The new reference point of the latitude is NOT sent through the vote, although a ray takes one only every ~6 km: the 32 or 64 rays of a wave take theirs on
+    //  different steps, so a wave would leave the loop on every fourth step - measured slower than the parent, 125 against 120 ms per pass.)
+    // POLE = false (the instantiations whose loop keeps the guard): without the second test.
+    static constexpr bool POLE_FAST = true;                         // the step loop has an unguarded fast step and a guarded one (rhs_g)
+    template <bool POLE>
+    static DEVINL void checks_fast(const GeoacDevParams& P, RayCtx& C, const double* y, const double* yn, int k, bool& brk, bool& gnd, bool& slow){
+        const double dl = yn[1] - C.a[0];
+        rot_small(C.a[1], C.a[2], dl, C.t[0], C.t[1]);
+        if(__builtin_expect(fabs(dl) > GEOAC_ROT_MAX, 0)){ C.a[0] = yn[1]; fsincos(yn[1], C.a[1], C.a[2]); C.t[0] = C.a[1]; C.t[1] = C.a[2]; }   // (rare, per ray: the rotation is discarded)
+        const double A = yn[1] - P.src[1] * kPi / 180.0, B = yn[2] - P.src[2] * kPi / 180.0;
+        const double q = __builtin_fma(fabs(P.src_trig[1] * C.t[1]), B * B, A * A);
+        slow = !(q < P.range_skip2);
+        if(POLE) slow = slow || !(fabs(C.t[0]) * P.pole_k <= fabs(C.t[1]));
+        brk = yn[0] > P.vert_limit;
+        gnd = yn[0] < P.ground;
+    }
+    // the pole_k test on the CURRENT row (the carried values after accept / restart / resume): true = the step from here runs guarded
+    static DEVINL bool near_pole(const GeoacDevParams& P, const RayCtx& C){ return !(fabs(C.cur[0]) * P.pole_k <= fabs(C.cur[1])); }
     static DEVINL void accept(RayCtx& C){ C.cur[0] = C.t[0]; C.cur[1] = C.t[1]; }
     static DEVINL void restart(const GeoacDevParams& P, RayCtx& C, const double* y){      // start of a leg: the reflected row is the new reference
         C.a[0] = y[1]; fsincos(y[1], C.a[1], C.a[2]);
@@ -1020,10 +1057,14 @@ struct EqGlobalPair : EqGlobal<true> {
     using Full = EqGlobal<true>;
     static constexpr int E = 12, LANES = 2;
     static constexpr bool SPLIT = true; static constexpr bool ROW_SPLIT = true;      // (the two lanes also store half a path row each)
+    template <bool GUARD, typename TabPtr>
+    static DEVINL void rhs_g(TabPtr tab, const GeoacDevParams& P, int& seg, const RayCtx& C, const double* y0, const double* yt, int stage, double* dy){
+        if(stage == 0) global_rhs<true, 1, true, GUARD>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], 0.0, dy, C.rcp0);
+        else global_rhs<true, 1, false, GUARD>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], yt[1] - y0[1], dy, C.rcp0);
+    }
     template <typename TabPtr>
     static DEVINL void rhs(TabPtr tab, const GeoacDevParams& P, int& seg, const RayCtx& C, const double* y0, const double* yt, int stage, double* dy){
-        if(stage == 0) global_rhs<true, 1, true>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], 0.0, dy, C.rcp0);
-        else global_rhs<true, 1>(tab, P, seg, C.rec, yt, C.cur[0], C.cur[1], yt[1] - y0[1], dy, C.rcp0);
+        rhs_g<true>(tab, P, seg, C, y0, yt, stage, dy);
     }
     // reflection of the base ray and of this lane's derivative system (Global.cpp:140-205, Q1 linear intercept)
     static DEVINL void reflect(const GeoacDevParams& P, const RayCtx& C, const double* yn, double* y, const double* ym2){
@@ -1516,6 +1557,8 @@ template <bool AMP_> struct Eq3D {
         brk = (yn[2] > P.vert_limit) || far;
         gnd = yn[2] < P.ground;
     }
+    static constexpr bool POLE_FAST = false;
+    static DEVINL void checks_fast(const GeoacDevParams& P, RayCtx& C, const double* y, const double* yn, int k, bool& brk, bool& gnd, bool& slow){ checks(P, C, y, yn, k, brk, gnd); slow = false; }   // (k_rk4's step loop: no row of this set needs more)
     static DEVINL void accept(RayCtx& C){}
     static DEVINL void resume(const GeoacDevParams& P, RayCtx& C, const double* y){}
     static DEVINL void restart(const GeoacDevParams& P, RayCtx& C, const double* y){}
@@ -1665,6 +1708,8 @@ template <bool AMP_> struct Eq2D {
         brk = (yn[1] > P.vert_limit) || (yn[0] > P.range_limit);
         gnd = yn[1] < P.ground;
     }
+    static constexpr bool POLE_FAST = false;
+    static DEVINL void checks_fast(const GeoacDevParams& P, RayCtx& C, const double* y, const double* yn, int k, bool& brk, bool& gnd, bool& slow){ checks(P, C, y, yn, k, brk, gnd); slow = false; }   // (k_rk4's step loop: no row of this set needs more)
     static DEVINL void accept(RayCtx& C){}
     static DEVINL void resume(const GeoacDevParams& P, RayCtx& C, const double* y){}
     static DEVINL void restart(const GeoacDevParams& P, RayCtx& C, const double* y){}
@@ -2037,8 +2082,16 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
         //    (row k-1, the three-stage sum, the last slope); the leg end is worked off outside and the wave re-enters.  Inside the loop a row is
         //    never merged with the outcome of a rare path, which is what cost ~45 register moves per step before (a few hundred leg ends per
         //    wave and fan against 50 000 steps).
+        //  * (spherical set) the tests a row rarely needs ride in the same vote: `slow` of EQ::checks_fast - the range test once the ray is within ~0.25 % of the
+        //    limit, a row from which the stage reciprocals need their pole guard.  The voted row runs the range test outside (EQ::range_far, the slow lanes
+        //    only: what a row's tests are depends on the ray's own rows, not on its wave's), and while a lane of the wave
+        //    stands on a row that failed the pole_k test the wave takes GUARDED steps one at a time - the same step with global_base's guard, straight into the
+        //    voted-row path - before it re-enters the fast loop, whose global_base has no guard.  Same bits on either path: DESIGN 3.
+        //    (The sample-capturing instantiations keep the guard in their loop and have no second step: with open_step's capture code twice they spill to scratch.
+        //     The Cartesian sets keep the loop they had, statement for statement - the shared form below moves their register allocation.)
+        if constexpr (!EQ::POLE_FAST){
         while(__any((nr + 2 <= P.s_rows) && !done)){                  // (wave-uniform)
-            bool ev = false, pend = false;
+            bool ev = false, pend = false, slow = false;
             double dy[E], ys[E], w6 = 0.0;                            // at a vote: the last slope, the sum of the first three stages, ds / 6
             if((nr + 2 <= P.s_rows) && !done) for(;;){                // (every lane that enters leaves at the same vote: no exec-mask bookkeeping inside)
                 open_step(y);
@@ -2061,11 +2114,11 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
                 double t[EQ::NB];
                 #pragma unroll
                 for(int e = 0; e < EQ::NB; e++) t[e] = __builtin_fma(dy[e], ds_6, ys[e]);
-                EQ::checks(P, C, y, t, k + 1, brk, gnd);
+                EQ::checks_fast(P, C, y, t, k + 1, brk, gnd, slow);        // (these sets: their checks, slow = false)
                 lim = (k + 1 >= k_lim);                               // Solver.cpp loop bound; never reached on sane inputs
                 ev = brk || gnd || lim;
                 const bool full = !(nr + 3 <= P.s_rows);                // this lane's chunk has no room for another step after this one
-                if(__builtin_expect(__any(ev || full), 0)){ pend = true; w6 = ds_6; break; }
+                if(__builtin_expect(__any(ev || full || slow), 0)){ pend = true; w6 = ds_6; break; }
                 #pragma unroll
                 for(int e = 0; e < E; e++){
                     if(YM2_REG) ym2[e] = y[e];
@@ -2087,6 +2140,78 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
                     for(int e = 0; e < E; e++){ if(YM2_REG) ym2[e] = y[e]; y[e] = ys[e]; }
                 }
             }
+        }
+        } else {
+        constexpr bool PF = !SMP;                                     // the fast loop runs without the pole guard, and a guarded step exists
+        while(__any((nr + 2 <= P.s_rows) && !done)){                  // (wave-uniform)
+            bool ev = false, pend = false, slow = false;
+            double dy[E], ys[E], w6 = 0.0;                            // at a vote: the last slope, the sum of the first three stages, ds / 6
+            // one step from row y up to the tests on its new row (dy, ys, the flags; returns ds / 6).  guard: BoolC<true> = with the pole guard
+            auto step_parts = [&](auto guard) -> double {
+                constexpr bool G = decltype(guard)::value;
+                auto rhs = [&](const double* yi, int stage){
+                    if(LDS) EQ::template rhs_g<G>(lds_tab, P, seg, C, y, yi, stage, dy); else EQ::template rhs_g<G>(gtab, P, seg, C, y, yi, stage, dy);
+                };
+                open_step(y);
+                const double ds = set_ds(EQ::above_ground(P, y), P.ds_min, P.ds_max);        // GeoAc_Set_ds (Global.cpp:210-217 and twins)
+                const double ds_2 = 0.5 * ds, ds_6 = (1.0 / 6.0) * ds, ds_3 = (1.0 / 3.0) * ds;
+                // k_s = ds f(y + a_s k_{s-1}), a = {0, 1/2, 1/2, 1};  y' = y + k1/6 + k2/3 + k3/3 + k4/6  (Solver.cpp:33-54)
+                double yt[E];
+                rhs(y, 0);
+                #pragma unroll
+                for(int e = 0; e < E; e++){ ys[e] = __builtin_fma(dy[e], ds_6, y[e]); yt[e] = __builtin_fma(dy[e], ds_2, y[e]); }
+                #pragma unroll 1
+                for(int stage = 1; stage < 3; stage++){
+                    rhs(yt, stage);
+                    const double wa = (stage == 2) ? ds : ds_2;
+                    #pragma unroll
+                    for(int e = 0; e < E; e++){ ys[e] = __builtin_fma(dy[e], ds_3, ys[e]); yt[e] = __builtin_fma(dy[e], wa, y[e]); }
+                }
+                rhs(yt, 3);                                           // (the last slope stays in dy)
+                // the position part of the new row and the tests on it (GeoAc_BreakCheck / GeoAc_GroundCheck / the loop bound)
+                double t[EQ::NB];
+                #pragma unroll
+                for(int e = 0; e < EQ::NB; e++) t[e] = __builtin_fma(dy[e], ds_6, ys[e]);
+                EQ::template checks_fast<PF>(P, C, y, t, k + 1, brk, gnd, slow);
+                lim = (k + 1 >= k_lim);                               // Solver.cpp loop bound; never reached on sane inputs
+                ev = brk || gnd || lim;
+                return ds_6;
+            };
+            const bool act = (nr + 2 <= P.s_rows) && !done;
+            bool guarded = false;
+            if constexpr (PF) guarded = __any(act && EQ::near_pole(P, C));
+            if(!guarded){
+                if(act) for(;;){                                      // (every lane that enters leaves at the same vote: no exec-mask bookkeeping inside)
+                    const double ds_6 = step_parts(BoolC<!PF>());
+                    const bool full = !(nr + 3 <= P.s_rows);            // this lane's chunk has no room for another step after this one
+                    if(__builtin_expect(__any(ev || full || slow), 0)){ pend = true; w6 = ds_6; break; }
+                    #pragma unroll
+                    for(int e = 0; e < E; e++){
+                        if(YM2_REG) ym2[e] = y[e];
+                        y[e] = __builtin_fma(dy[e], ds_6, ys[e]);
+                    }
+                    k++; steps_here++;
+                    put_row(y);
+                    EQ::accept(C);
+                }
+            } else if constexpr (PF){ if(act){ w6 = step_parts(BoolC<true>()); pend = true; } }      // (rare: a wave with a ray beyond the pole_k latitude)
+            if(pend){                                                 // (rare) the row that was voted on
+                #pragma unroll
+                for(int e = 0; e < E; e++) ys[e] = __builtin_fma(dy[e], w6, ys[e]);
+                if(slow){                                             // the range test on the same row (its position is in ys now, the bits the fast tests saw; its sin / cos of latitude in C.t)
+                    brk = EQ::range_far(P, C, ys[2] - P.src[2] * kPi / 180.0) || brk;
+                    ev = brk || gnd || lim;
+                }
+                k++; steps_here++;
+                put_row(ys);
+                EQ::accept(C);                                        // (a leg end sets the carried values anew: restart)
+                if(ev) leg_end(y, ys, ym2);
+                else {
+                    #pragma unroll
+                    for(int e = 0; e < E; e++){ if(YM2_REG) ym2[e] = y[e]; y[e] = ys[e]; }
+                }
+            }
+        }
         }
     } else {
     // COOP: wave-uniform loop (every lane stays while any lane of the wave has work; `act` predicates this lane's own work).

@@ -41,6 +41,12 @@ int geoac_probe_absorption_table(geoac_ctx* ctx, int n, const double* x, double*
  * d/da2 of c, u, v through the scalar evaluators.  coop != 0: through the wave-cooperative gather the dense grid fans use. */
 int geoac_probe_grid(geoac_ctx* ctx, int n, const double* a0, const double* a1, const double* a2, int coop, double* out30, double* api7);
 
+/* spherical stratified set: the two constants behind the step loop's cheap per-row tests, as a launch with these parameters sets them (no context, no
+ * device: host arithmetic).  out[5]: range_thresh = sin^2(range_limit / 2 r_earth); range_skip2 - the range test cannot fire on a row with
+ * dlat^2 + |cos(lat_src) cos(lat)| dlon^2 below it; pole_k - a step from a row with |sin(lat)| pole_k <= |cos(lat)| needs no guard on its stage reciprocals;
+ * the guard's threshold; delta, the bound on a stage's latitude increment that pole_k is derived with.  ground_radius = r_earth + z_grnd. */
+void geoac_probe_step_vote_consts(double range_limit, double r_earth, double ground_radius, double ds_min, double ds_max, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,8 +114,11 @@ def main():
             if not s or s.startswith(".") or s.endswith(":"):
                 continue
             ins.append(s)
-        # the step loop: the unconditional backward branch whose span holds the most FP64 instructions
-        best = None
+        # the step loop: among the unconditional backward branches, a loop whose COMMON PATH (the walk below, in-line blocks skipped) comes back to its own back
+        # edge and is dense in FP64 (>= 80 %); of those with at least half the FP64 instructions of the largest, the shortest walk - the loops around the step
+        # loop hold it and the rare paths too (leg ends, the voted row, the guarded step), the rolled stage loop inside holds a quarter of it.
+        # Without such a loop: the span that is densest in FP64, as before.
+        best, cands = None, []
         for i, s in enumerate(ins):
             m = re.match(r"^s_branch\s+(\.LBB\d+_\d+)", s)
             if m and m.group(1) in labels and labels[m.group(1)] < i:
@@ -124,6 +127,14 @@ def main():
                 score = float(n) ** 3 / float(i - h + 1) ** 2              # (dense in FP64: the step loop, not the loops around it that also hold the leg ends)
                 if best is None or score > best[2]:
                     best = (h, i, score)
+                cnt, pth = trace(ins, labels, h, i, True, 1)
+                tot = sum(cnt.values())
+                if pth and pth[-1] == i and min(pth) >= h and max(pth) <= i and cnt["fp64"] >= 0.8 * tot:      # (a walk that leaves the span is not this loop's)
+                    cands.append((h, i, cnt["fp64"], tot))
+        if cands:
+            big = max(c[2] for c in cands)
+            h, i, _, _ = min((c for c in cands if 2 * c[2] >= big), key=lambda c: c[3])
+            best = (h, i, 0.0)
         h, t, _ = best
         trips = 1
         for a in sys.argv:
