@@ -652,7 +652,7 @@ DEVINL double suthbass_alpha(const GeoacDevParams& P, double zr, double c_snd, d
 // far inside the spacing of the doubles next to 1, so 1 + N rounds as in the exact routine.  k_atab_build samples the pieces from the
 // exact routine itself (inside a spline segment the medium is a cubic and the pieces analytic) and checks the reassembled alpha against
 // it at eight other points of the segment: an entry that misses 1e-10 relative anywhere (a branch point of the reference's piecewise
-// fits inside the segment, a very long segment) is flagged, and the post-pass evaluates the segments that fall into it exactly (fix-up
+// fits inside the segment, a very long segment), or whose N piece is not close enough to round as the exact N does where a step of the staircase matters, is flagged, and the post-pass evaluates the segments that fall into it exactly (fix-up
 // pass of k_postpass).  Two more entries cover the strips just below the first and above the last node, where the reference clamps
 // the medium but not the height (the row below the ground, the row above the top).
 // ------------------------------------------------------------------------------------------------
@@ -2837,6 +2837,15 @@ __global__ void __launch_bounds__(64) k_atab_build(GeoacDevParams P, double* __r
         const double err = fabs(px - fx) / fabs(fx);
         if(!(err <= tol)) ok = false;
         worst = (err > worst) ? err : worst;
+        // The staircase (see above) is reproduced only while 1 + N rounds as in the exact routine, and alpha within tol does not say so: the N piece is held
+        // to its own bound.  Its interpolant misses the exact N by dN; 1 + N (spacing of the doubles there: 2^-52) then rounds the other way on a share
+        // dN / 2^-52 of the abscissae, and each such abscissa is off by one step of sqrt(1 + N) - 1 = N / 2: 2^-52 / N of the classical term.  Where a step is
+        // worth more than the 10 tol the table is held to between its check points (N < 2e-7 at the default tolerance: below ~101 km at 0.1 Hz), that share
+        // must stay below 5e-4 - 0.1 km segments have 3e-4 at most there at any frequency (dN <= 3e-13 N), a 0.28 km segment at 99 km 2e-2 (dN = 6e-11 N).
+        double pr[3];
+        exact(chk[q], pr);
+        const double dN = fabs(atab_poly(o + 7, chk[q]) - pr[1]);
+        if(pr[1] > 0.0 && 0x1p-52 > 10.0 * tol * pr[1] && dN > 5e-4 * 0x1p-52) ok = false;
     }
     if(!ok) o[0] = -o[0];                                       // flagged: not served
     o[GEOAC_ATABW - 1] = worst;

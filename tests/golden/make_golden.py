@@ -4,6 +4,7 @@ by oracle/Makefile from /root/reference).  Run here only (the reference does not
     make -C oracle all && python tests/golden/make_golden.py            # {global,3d,2d}_small.npz; `rngdep`, `globalrd`: the grid sets'
     python tests/golden/make_golden.py polar                            # global_polar.npz (3 minutes on one core)
     python tests/golden/make_golden.py globalrd_polar                   # globalrd_polar.npz (2 minutes)
+    python tests/golden/make_golden.py jet                              # jet_small.npz: the stratified sets on tests/golden/JetAtmo.met (`zuvwTdp`; 4 minutes on three cores)
 
 The fixtures are data: launch angles + configuration in, full-precision arrival records / samples /
 probe values out.  tests/test_oracle_golden.py pins the plain-C oracle to them bit for bit;
@@ -278,8 +279,129 @@ def main_globalrd_polar():
     print("globalrd_polar ->", path, os.path.getsize(path) // 1024, "KiB")
 
 
+# ---- the stratified sets on a jet profile with meridional wind, read through the second profile format (tests/test_gpu_jet.py, test_oracle_golden.py) ----
+# tests/golden/JetAtmo.met (tests/jet_data.py, `zuvwTdp`): u up to 85 m/s, v = 40 / -22 / 15 m/s.  Two fans per set, azimuths all round (the v sin(phi) and
+# ny v terms vanish at +-90): (a) from the ground, (b) from 12 km - wind AT the source (u = 30, v = -22 m/s: the initial slowness and the amplitude's m0.u,
+# m0.v, quirk Q4) - with rays launched below the horizontal.  range_limit = JET_RANGE keeps the longest leg of the Cartesian sets near 1e5 steps (ducted
+# rays in the jets run to the limit and BREAK there: an exact step count is part of what is pinned).
+JET_TH_A = [2.0, 7.0, 19.0, 34.0]
+JET_TH_B = [-20.0, -8.0, -2.0, 1.0, 6.0, 12.0, 18.0, 25.0, 33.0, 41.0]
+JET_AZ = [-180.0, -135.0, -90.0, -45.0, 0.0, 45.0, 90.0, 135.0]
+JET_RANGE = 2000.0
+
+
+# Rays left out of the lattice (theta, azimuth): they fail the conditioning assertion of main_jet on the compiled reference in at least one set - the reference's
+# own answer to theta (1 + 1e-12) moves a compared field by more than 2.5e-7 there, so no arithmetic but its own bit pattern follows it to 1e-6.
+#   a ( 7, -135)  3D / 2D: grazes the top of the tropospheric duct; the perturbed ray's second leg changes its STEP COUNT (STATE moves by 8e-2)
+#   a ( 2,    0), a (2, -180)  Global: third leg, 9.7e-7 and 8.4e-7 (launch-angle derivatives of rays that bounce three times inside the duct)
+#   b (33,   45)  3D / 2D: 6.3e-6 / 4.8e-7 on the third leg (turns at the edge of the stratospheric jet)
+#   b (12,  135), b (12, 90), b (1, -180)  Global: 2.9e-5, 1.4e-6 (third legs) and 5.1e-7 (the ducted ray itself, ATTEN after 42 683 steps)
+JET_DROPPED = {"a": [(7.0, -135.0), (2.0, 0.0), (2.0, -180.0)], "b": [(33.0, 45.0), (12.0, 135.0), (12.0, 90.0), (1.0, -180.0)]}
+
+
+def jet_fans():
+    import jet_data as JD
+    out = {}
+    for name, ths, z in (("a", JET_TH_A, 0.0), ("b", JET_TH_B, JD.SRC_Z)):
+        rays = [(t, a) for a in JET_AZ for t in ths if (t, a) not in JET_DROPPED[name]]
+        out[name] = (np.array([r[0] for r in rays]), np.array([r[1] for r in rays]), z)
+    return out
+
+
+def _jet_set(eq):
+    """one set's share of jet_small.npz (runs in a process of its own): (record tables, atmosphere probes, printed lines, failures)"""
+    import jet_data as JD
+    from parity import field_errors
+    sname = H.EQ_NAMES[eq]
+    fans = jet_fans()
+    out, lines, failures = {}, [], []
+    R, O = H.RefShim(eq, met=JD.JET, fmt=JD.FMT), H.Oracle(eq, met=JD.JET, fmt=JD.FMT)
+    for tag, (fan, kw) in JD.TABLES.items():
+        th, ph, z = fans[fan]
+        cfg = H.make_cfg(eq, src=JD.src(eq, z), range_limit=JET_RANGE, **kw)
+        steps, rec, _, _ = R.fan(cfg, th, ph)
+        so, ro, _, _ = O.fan(cfg, th, ph)
+        assert so == steps and np.array_equal(ro, rec), f"{sname} {tag}: the oracle's records differ from the compiled reference's"
+        sp, rp, _, _ = R.fan(cfg, th * (1.0 + POLAR_SENS_EPS), ph)
+        moved = np.flatnonzero((rp[..., :3] != rec[..., :3]).any(axis=(1, 2)))
+        E = JD.ESIZE[eq][1 if kw["calc_amp"] else 0]
+        fe = field_errors(rp, rec, E, JD.HIDX[eq])
+        fields = sorted(fe)
+        sens = np.stack([fe[f] for f in fields], axis=-1)
+        worst = {f: float(np.nanmax(fe[f])) for f in fields}
+        per_ray = np.nanmax(np.nan_to_num(sens), axis=(1, 2))
+        valid = rec[..., H.REC["VALID"]] > 0
+        lines.append(f"{sname} {tag}: {steps} steps, {int(valid.sum())} arrivals ({int(valid[th < 0].sum())} of rays launched downwards), {int((rec[..., H.REC['BROKE']] > 0).sum())} legs BROKE, "
+                     f"longest leg {int(rec[..., H.REC['STEPS']].max())} steps; worst sensitivity " + ", ".join(f"{f} {v:.1e}" for f, v in worst.items()))
+        if len(moved):
+            failures.append(f"{sname} {tag}: VALID / STEPS / BROKE move with theta (1 + {POLAR_SENS_EPS:g}) on rays {[(th[i], ph[i]) for i in moved]}")
+        if not 4.0 * np.nanmax(sens) <= 1e-6:
+            failures.append(f"{sname} {tag}: the reference itself is ill-conditioned on rays {[(th[i], ph[i], float(per_ray[i])) for i in np.flatnonzero(per_ray > 2.5e-7)]}: {worst}")
+        key = f"{sname}_{tag}"
+        if tag == "b_f001":
+            # the frequency enters the absorption alone: every other column is b_amp1's, bit for bit - the fixture holds the ATTEN column (jet_data.table puts the table together)
+            other = np.arange(H.REC_STRIDE) != H.REC["ATTEN"]
+            assert np.array_equal(rec[..., other], out[f"{sname}_b_amp1_rec"][..., other]), f"{sname}: freq changes more than ATTEN"
+            out[f"{key}_atten"] = rec[..., H.REC["ATTEN"]]
+        else:
+            out[f"{key}_rec"] = rec
+        out[f"{key}_steps"] = np.int64(steps)
+        out[f"{key}_sens"] = sens.astype(np.float32); out[f"{key}_sens_fields"] = np.array(fields)
+    # atmosphere + absorption probes, as main(): nodes, both ends, beyond both ends - and points on and next to the 3 .. 10 m segments
+    t = R.tables()
+    rng = np.random.default_rng(12345)
+    x = rng.uniform(t["x"][0] - 0.5, t["x"][-1] + 0.5, 1000)
+    x[:8] = [t["x"][0], t["x"][-1], t["x"][1], t["x"][700], t["x"][0] - 1, t["x"][-1] + 1, t["x"][3], t["x"][4]]
+    k = np.flatnonzero(np.diff(t["x"]) < 0.011)[:30]
+    assert len(k) == 30
+    x[8:128] = np.concatenate([t["x"][k], t["x"][k + 1], 0.5 * (t["x"][k] + t["x"][k + 1]), t["x"][k] - 1e-9])
+    o9, rho = R.atmo_probe(x)
+    oo9, orho = O.atmo_probe(x)
+    assert np.array_equal(oo9, o9) and np.array_equal(orho, rho), f"{sname}: the oracle's spline accessors differ from the compiled reference's"
+    xa = rng.uniform(t["x"][0], t["x"][-1], 200)
+    fa = 10.0 ** rng.uniform(-2, 1, 200)
+    alpha = R.absorption_probe(xa, fa, 0.0, 0.3)
+    assert np.array_equal(O.absorption_probe(xa, fa, 0.0, 0.3), alpha), f"{sname}: the oracle's absorption differs from the compiled reference's"
+    atmo = dict(probe_x=x, probe_out9=o9, probe_rho=rho, abs_x=xa, abs_f=fa, abs_alpha=alpha, **{f"tab_{k}": v for k, v in t.items()})
+    return out, atmo, lines, failures
+
+
+def main_jet():
+    """jet_small.npz: per set (a process each: the reference holds one profile per set), table and field the compiled reference's records and step total - the
+    oracle asserted equal bit for bit - and `sens`, as main_polar stores it: 4 x sens <= 1e-6 asserted for every field of every arrival, the counts asserted
+    unchanged under theta (1 + 1e-12).  Plus the probes of test_gpu_probes.py on this profile and the reference's spline tables.  The Cartesian sets
+    share G2S_Spline1D.cpp: their tables and probe values are asserted identical and stored once (`cart_`)."""
+    import jet_data as JD
+    from concurrent.futures import ProcessPoolExecutor
+    eqs = (H.EQ_GLOBAL, H.EQ_3D, H.EQ_2D)
+    out = {"range_limit": np.float64(JET_RANGE), "sens_eps": np.float64(POLAR_SENS_EPS), "src_z": np.float64(JD.SRC_Z)}
+    for name, (th, ph, z) in jet_fans().items():
+        out[f"{name}_theta"] = th; out[f"{name}_phi"] = ph
+    with ProcessPoolExecutor(max_workers=3) as pool:
+        res = dict(zip(eqs, pool.map(_jet_set, eqs)))
+    failures = []
+    for eq in eqs:
+        out.update(res[eq][0])
+        print("\n".join(res[eq][2]))
+        failures += res[eq][3]
+    assert not failures, "\n".join(failures)
+    for k, v in res[H.EQ_3D][1].items():
+        assert np.array_equal(v, res[H.EQ_2D][1][k]), f"{k}: the 2-D set's value differs from the 3-D set's"
+        out[f"cart_{k}"] = v
+    for k, v in res[H.EQ_GLOBAL][1].items():
+        if k in ("tab_T", "tab_rho"):                 # (no set changes T or rho on loading: stored once)
+            assert np.array_equal(v, out[f"cart_{k}"]), f"{k}: the Global set's value differs from the Cartesian sets'"
+        else:
+            out[f"global_{k}"] = v
+    path = os.path.join(OUT, "jet_small.npz")
+    np.savez_compressed(path, **out)
+    print("jet ->", path, os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "polar":
+    if len(sys.argv) > 1 and sys.argv[1] == "jet":
+        main_jet()
+    elif len(sys.argv) > 1 and sys.argv[1] == "polar":
         main_polar()
     elif len(sys.argv) > 1 and sys.argv[1] == "globalrd_polar":
         main_globalrd_polar()

@@ -27,7 +27,12 @@ CASES = {
     # range-dependent spherical main on the synthetic lat/lon grid: -prop g loc_lat.dat loc_lon.dat ... (default source = grid centre)
     "globalrd": ("GeoAcGlobal.RngDep", ["theta_min=10", "theta_max=30", "theta_step=20", "phi_min=-90", "phi_max=-45", "phi_step=45",
                                         "bounces=1", "WriteCaustics=True", "WriteAtmo=True", "z_src=0.5", "lon_src=1.25"]),
+    # the second profile format on the jet profile (tests/jet_data.py): 2 x 2 fan from 12 km, where the wind is 30 / -22 m/s; azimuths 45 and 135: both wind components act along and across the rays
+    "3d_jet": ("GeoAc3D", ["profile_format=zuvwTdp", "theta_min=25", "theta_max=41", "theta_step=16", "phi_min=45", "phi_max=135", "phi_step=90",
+                           "bounces=0", "z_src=12", "rng_max=450"]),
 }
+# the profile a case reads where it is not ToyAtmo.met (kept as the file MET beside ARGS)
+CASE_MET = {"3d_jet": "JetAtmo.met"}
 
 
 # eigenray modes of the spherical mains: (binary, option, args); the verbose stdout is kept as LOG.txt
@@ -146,8 +151,9 @@ def main():
                 RD.write_grid(td)
                 inputs = ["p", "loc_x.dat", "loc_y.dat"]
             else:
-                shutil.copy(os.path.join(HERE, "ToyAtmo.met"), os.path.join(td, "ToyAtmo.met"))
-                inputs = ["ToyAtmo.met"]
+                met = CASE_MET.get(name, "ToyAtmo.met")
+                shutil.copy(os.path.join(HERE, met), os.path.join(td, met))
+                inputs = [met]
             subprocess.run([os.path.join(REF, binary), "-prop"] + inputs + args, cwd=td, check=True,
                            stdout=subprocess.DEVNULL)
             for f in sorted(os.listdir(td)):
@@ -155,6 +161,9 @@ def main():
                     shutil.copy(os.path.join(td, f), os.path.join(out, f))
         with open(os.path.join(out, "ARGS"), "w") as fh:
             fh.write(binary + "\n" + "\n".join(args) + "\n")
+        if name in CASE_MET:
+            with open(os.path.join(out, "MET"), "w") as fh:
+                fh.write(CASE_MET[name] + "\n")
         print(name, sorted(os.listdir(out)), sum(os.path.getsize(os.path.join(out, f)) for f in os.listdir(out)) // 1024, "KiB")
 
 

@@ -12,7 +12,7 @@
 #define CHECK(c) do { if(!(c)){ fprintf(stderr, "CHECK failed: %s (line %d)\n", #c, __LINE__); return 1; } } while(0)
 
 int main(int argc, char** argv){
-    if(argc < 5){ fprintf(stderr, "usage: san_host_driver ToyAtmo.met grid_prefix loc_x loc_y\n"); return 2; }
+    if(argc < 5){ fprintf(stderr, "usage: san_host_driver ToyAtmo.met grid_prefix loc_x loc_y [seven_column.met]\n"); return 2; }
     const char* met = argv[1];
     // ---- 1-D profile ----
     for(int eq : {GEOAC_EQ_2D, GEOAC_EQ_3D, GEOAC_EQ_GLOBAL}){
@@ -30,6 +30,28 @@ int main(int argc, char** argv){
         CHECK(std::isfinite(c[0] + c[1] + c[2] + c[3]));
     }
     CHECK(geoac_met_rows("/nonexistent/file.met") <= 0);
+    // ---- the second profile format: z u v w T rho p, seven columns a row ----
+    if(argc > 5){
+        const char* met7 = argv[5];
+        for(int eq : {GEOAC_EQ_2D, GEOAC_EQ_3D, GEOAC_EQ_GLOBAL}){
+            int n = geoac_met_rows(met7);
+            CHECK(n >= 3);
+            std::vector<double> x(n), T(n), u(n), v(n), rho(n);
+            CHECK(geoac_met_load(met7, "zuvwTdp", eq, n, x.data(), T.data(), u.data(), v.data(), rho.data()) == n);
+            for(int i = 0; i < n; i++){
+                CHECK(T[i] > 100.0 && T[i] < 2000.0 && rho[i] > 0.0 && rho[i] < 0.01);              // (the fifth and sixth columns, not the w column)
+                CHECK(std::fabs(u[i]) < 0.5 && std::fabs(v[i]) < 0.5);                              // km/s
+                CHECK(i == 0 || x[i] > x[i - 1]);
+            }
+            CHECK(geoac_met_load_zg(met7, "zuvwTdp", eq, 0.3, n, x.data(), T.data(), u.data(), v.data(), rho.data()) == n);
+            CHECK(geoac_met_load(met7, "zuvwTdp", eq, n - 1, x.data(), T.data(), u.data(), v.data(), rho.data()) == -4);     // capacity too small
+            CHECK(geoac_met_load(met7, "zuvwTd", eq, n, x.data(), T.data(), u.data(), v.data(), rho.data()) == -2);
+            // a six-column file read as seven columns runs out of numbers before its rows end: the missing values are zeros, nothing is read past the file
+            std::vector<double> x6(1400), T6(1400), u6(1400), v6(1400), rho6(1400);
+            CHECK(geoac_met_load(met, "zuvwTdp", eq, 1400, x6.data(), T6.data(), u6.data(), v6.data(), rho6.data()) == 1400);
+            CHECK(T6[1399] == 0.0 && rho6[1399] == 0.0);
+        }
+    }
     // ---- launch-angle enumeration (repeated addition, as the reference's loops) ----
     long n = geoac_fan_enumerate(0.5, 45.0, 0.5, -180.0, 179.0, 1.0, 0, nullptr, nullptr);
     CHECK(n == 32400);

@@ -41,7 +41,7 @@ def _compare_files(got, want):
     return nsame, ntok
 
 
-@pytest.mark.parametrize("case", ["global", "3d", "2d", "cfg1", "global_norays", "3drd", "globalrd", "global+groups", "3drd+groups", "3drd+sub", "global+1thread", "globalrd+1thread"])
+@pytest.mark.parametrize("case", ["global", "3d", "2d", "cfg1", "global_norays", "3drd", "globalrd", "global+groups", "3drd+groups", "3drd+sub", "global+1thread", "globalrd+1thread", "3d_jet"])
 def test_cli_files_match_reference_binaries(case, tmp_path):
     """"+groups": the same fan integrated one azimuth group at a time (the path large WriteRays fans take: bounded sample list, text of
     group g written while group g+1 is on the GPU) must give the same files.  "+sub": the launch plan of saturated grid fans forced on the
@@ -74,8 +74,9 @@ def test_cli_files_match_reference_binaries(case, tmp_path):
         RD.write_grid(str(tmp_path), short_paths=False)      # the driver is run with relative names from cwd
         inputs = ["p", "loc_x.dat", "loc_y.dat"]
     else:
-        shutil.copy(H.TOYATMO, tmp_path / "ToyAtmo.met")
-        inputs = ["ToyAtmo.met"]
+        met = open(os.path.join(gold, "MET")).read().strip() if os.path.exists(os.path.join(gold, "MET")) else "ToyAtmo.met"      # (3d_jet: JetAtmo.met, profile_format=zuvwTdp)
+        shutil.copy(os.path.join(H.GOLDEN_DIR, met), tmp_path / met)
+        inputs = [met]
     subprocess.run([exe, "-prop"] + inputs + params + gpu_args, cwd=tmp_path, check=True, stdout=subprocess.DEVNULL, env=env)
     want_files = sorted(f for f in os.listdir(gold) if f.endswith(".dat"))
     got_files = sorted(f for f in os.listdir(tmp_path) if f.endswith(".dat") and not f.startswith("loc_"))

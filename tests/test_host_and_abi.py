@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import harness as H
+import jet_data as JD
 
 import geoac_amd as G
 
@@ -88,6 +89,57 @@ def test_met_load_with_ground_taper(lib):
     w = (2.0 / (1.0 + np.exp(-((raw[:, 0] + 6370.0) - 6370.0 - 0.3) / 0.2)) - 1.0) / 1000.0
     assert np.allclose(u1, raw[:, 2] * w, rtol=1e-14, atol=0) and np.allclose(v1, raw[:, 3] * w, rtol=1e-14, atol=0)
     assert np.array_equal(T1, T0) and np.array_equal(r1, r0)
+
+
+def _met_load_zg(lib, path, fmt, eq, zg):
+    n = lib.geoac_met_rows(path.encode())
+    dp = ctypes.POINTER(ctypes.c_double)
+    a = [np.zeros(max(n, 1)) for _ in range(5)]
+    lib.geoac_met_load_zg.argtypes = None
+    rc = lib.geoac_met_load_zg(path.encode(), fmt.encode(), eq, ctypes.c_double(zg), n, *[x.ctypes.data_as(dp) for x in a])
+    return rc, dict(zip(("x", "T", "u", "v", "rho"), a))
+
+
+@pytest.mark.parametrize("eq", [H.EQ_GLOBAL, H.EQ_3D, H.EQ_2D])
+def test_second_profile_format_matches_reference_tables_and_its_twin(lib, eq, tmp_path):
+    """`zuvwTdp` (z, u, v, w, T, rho, p) on tests/golden/JetAtmo.met: the five arrays and the spline slopes are the compiled reference's own tables
+    (tests/golden/jet_small.npz, which the reference loaded through its own zuvwTdp branch) bit for bit, and the bits of the same numbers read from a
+    `zTuvdp` file.  The file's w column is not zero: it may appear in no output."""
+    g = np.load(JD.FIXTURE)
+    a = G.met_load(JD.JET, eq, fmt=JD.FMT)
+    for k in ("x", "T", "u", "v", "rho"):
+        assert np.array_equal(a[k], JD.atmo(g, eq, f"tab_{k}")), k
+    for k, f in (("sT", "T"), ("su", "u"), ("sv", "v"), ("srho", "rho")):
+        assert np.array_equal(G.natural_spline_slopes(a["x"], a[f]), JD.atmo(g, eq, f"tab_{k}")), k
+    b = G.met_load(JD.write_twin(str(tmp_path / "twin.met")), eq)
+    for k in ("x", "T", "u", "v", "rho"):
+        assert np.array_equal(a[k], b[k]), k
+    raw = JD.load_columns()
+    assert (raw["w"] != 0.0).all() and np.abs(raw["w"]).max() > 0.2 and np.abs(raw["v"]).max() > 30.0 and raw["v"].min() < -15.0 and raw["u"].max() > 30.0 and raw["u"].min() < -20.0
+    assert np.array_equal(a["T"], raw["T"]) and np.array_equal(a["rho"], raw["rho"])
+    rc, a0 = _met_load_zg(lib, JD.JET, JD.FMT, eq, 0.0)
+    assert rc == len(raw["z"]) and all(np.array_equal(a0[k], a[k]) for k in a)
+
+
+@pytest.mark.parametrize("eq", [H.EQ_GLOBAL, H.EQ_3D, H.EQ_2D])
+def test_second_profile_format_with_ground_taper(lib, eq):
+    """geoac_met_load_zg with `zuvwTdp` and z_grnd = 0.3: the taper formula of test_met_load_with_ground_taper on the file's u and v columns (the second
+    and third), T and rho untouched"""
+    raw = JD.load_columns()
+    rc, a = _met_load_zg(lib, JD.JET, JD.FMT, eq, 0.3)
+    assert rc == len(raw["z"])
+    x = raw["z"] + (6370.0 if eq == H.EQ_GLOBAL else 0.0)
+    w = (2.0 / (1.0 + np.exp(-((x - 6370.0 if eq == H.EQ_GLOBAL else x) - 0.3) / 0.2)) - 1.0) / 1000.0
+    assert np.array_equal(a["x"], x)
+    assert np.allclose(a["u"], raw["u"] * w, rtol=1e-14, atol=0) and np.allclose(a["v"], raw["v"] * w, rtol=1e-14, atol=0)
+    assert np.array_equal(a["T"], raw["T"]) and np.array_equal(a["rho"], raw["rho"])
+    assert np.abs(a["v"]).max() > 0.03                                  # (km/s: the comparison is not of noise)
+
+
+def test_unknown_profile_format_is_refused(lib):
+    for fmt in ("zuvwTd", "zTuvd", "ZUVWTDP", "", "zwuvTdp"):
+        assert _met_load_zg(lib, JD.JET, fmt, H.EQ_3D, 0.0)[0] == -2, fmt
+        assert _met_load_zg(lib, H.TOYATMO, fmt, H.EQ_GLOBAL, 0.3)[0] == -2, fmt
 
 
 def test_drivers_print_usage_without_arguments(lib):

@@ -63,3 +63,54 @@ def test_spherical_grid_host_evaluator_vs_reference_probes(tmp_path):
     scale = np.abs(api[:, 2:4]).max()
     assert np.abs(ev(1, plat, plon, pr) - api[:, 2]).max() < 1e-12 * scale
     assert np.abs(ev(2, plat, plon, pr) - api[:, 3]).max() < 1e-12 * scale
+
+
+def _write_grid_files(dirpath, fmt, glob):
+    """the committed 5 x 5 grid columns (rngdep_data) as <prefix><n>.met in either column order; the seven-column files carry a non-zero w column"""
+    import os
+    os.makedirs(dirpath, exist_ok=True)
+    if glob:
+        g = np.load(RD.GRID_GLOBAL_NPZ)
+        z, T, u, v, rho, p, ax, ay = g["z"], g["T"], g["u"], g["v"], g["rho"], g["p"], RD.LAT_NODES, RD.LON_NODES
+    else:
+        z, T, u, v, rho, p = RD.load_grid_columns()
+        ax, ay = RD.X_NODES, RD.Y_NODES
+    prefix = os.path.join(dirpath, "q")
+    for i in range(len(ax)):
+        for j in range(len(ay)):
+            with open(f"{prefix}{i * len(ay) + j}.met", "w") as fh:
+                for k in range(len(z)):
+                    c = dict(z=f"{z[k]:.10g}", T=f"{T[i, j, k]:.12g}", u=f"{u[i, j, k]:.12g}", v=f"{v[i, j, k]:.12g}", d=f"{rho[i, j, k]:.12g}", p=f"{p[k]:.10g}",
+                             w=f"{0.7 + 0.01 * k + i - j:.6g}")
+                    fh.write(" ".join(c[q] for q in ("zTuvdp" if fmt == "zTuvdp" else "zuvwTdp")) + "\n")
+    locx, locy = os.path.join(dirpath, "loc_a.dat"), os.path.join(dirpath, "loc_b.dat")
+    open(locx, "w").write("".join(f"{x:.10g}\n" for x in ax))
+    open(locy, "w").write("".join(f"{y:.10g}\n" for y in ay))
+    return prefix, locx, locy
+
+
+@pytest.mark.parametrize("eq", [G.EQ_3D_RNGDEP, G.EQ_GLOBAL_RNGDEP])
+@pytest.mark.parametrize("z_grnd", [0.0, 0.3])
+def test_grid_loader_reads_both_profile_formats_alike(eq, z_grnd, tmp_path):
+    """geoac_grid_load_eq on the same numbers written as `zTuvdp` and as `zuvwTdp` files: the ten outputs (return value, three axes, four fields... and the
+    dimensions) are the same bits - no column of the seven-column rows is mistaken for another, the w column goes nowhere"""
+    lib = G.load_library()
+    lib.geoac_grid_load_eq.argtypes = None
+    got = {}
+    for fmt in ("zTuvdp", "zuvwTdp"):
+        grid = _write_grid_files(str(tmp_path / fmt), fmt, eq == G.EQ_GLOBAL_RNGDEP)
+        nx, ny, nz = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        assert lib.geoac_grid_dims(grid[0].encode(), grid[1].encode(), grid[2].encode(), ctypes.byref(nx), ctypes.byref(ny), ctypes.byref(nz)) == 0
+        dims = (nx.value, ny.value, nz.value)
+        ax = [np.full(n, np.nan) for n in dims]
+        F = [np.full(dims, np.nan) for _ in range(4)]
+        assert lib.geoac_grid_load_eq(eq, grid[0].encode(), grid[1].encode(), grid[2].encode(), fmt.encode(), ctypes.c_double(z_grnd),
+                                      *dims, *[_p(a) for a in ax], *[_p(f) for f in F]) == 0
+        assert lib.geoac_grid_load_eq(eq, grid[0].encode(), grid[1].encode(), grid[2].encode(), b"zuvwTd", ctypes.c_double(z_grnd),
+                                      *dims, *[_p(a) for a in ax], *[_p(f) for f in F]) == -2
+        got[fmt] = (dims, ax + F)
+    assert got["zTuvdp"][0] == got["zuvwTdp"][0] == (5, 5, 350)
+    for a, b in zip(got["zTuvdp"][1], got["zuvwTdp"][1]):
+        assert np.isfinite(a).all() and np.array_equal(a, b)
+    T, u, v = got["zuvwTdp"][1][3:6]
+    assert T.min() > 100.0 and np.abs(u).max() < 0.2 and np.abs(v).max() < 0.2 and np.abs(u).max() > 0.01      # K and km/s: T is the fifth column

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import harness as H
+import jet_data as JD
 
 EQS = [H.EQ_GLOBAL, H.EQ_3D, H.EQ_2D]
 
@@ -78,3 +79,39 @@ def test_fan_enumeration_matches_reference_loop():
     assert len(th) == 449
     th, ph = H.fan_angles(phi_min=-180.0, phi_max=179.0, phi_step=1.0)
     assert len(th) == 360 * 90
+
+
+# ---- the jet profile with meridional wind, read through the second profile format (tests/golden/jet_small.npz, make_golden.py `jet`) ----
+# The oracle only: the compiled reference holds one profile per set and process, and other tests hold ToyAtmo there.
+@pytest.fixture(scope="module")
+def jet():
+    return np.load(JD.FIXTURE)
+
+
+@pytest.fixture(scope="module")
+def jet_oracles():
+    return {eq: H.Oracle(eq, met=JD.JET, fmt=JD.FMT) for eq in EQS}
+
+
+@pytest.mark.parametrize("eq", EQS)
+@pytest.mark.parametrize("tag", list(JD.TABLES))
+def test_jet_fan_records_bitexact(eq, tag, jet, jet_oracles):
+    th, ph, z = JD.fan(jet, tag)
+    want, want_steps, _ = JD.table(jet, eq, tag)
+    cfg = H.make_cfg(eq, src=JD.src(eq, z), range_limit=float(jet["range_limit"]), **JD.TABLES[tag][1])
+    steps, rec, _, _ = jet_oracles[eq].fan(cfg, th, ph)
+    assert steps == want_steps
+    assert np.array_equal(rec, want)
+
+
+@pytest.mark.parametrize("eq", EQS)
+def test_jet_tables_and_probes_bitexact(eq, jet, jet_oracles):
+    O = jet_oracles[eq]
+    t = O.tables()
+    for k in t:
+        assert np.array_equal(t[k], JD.atmo(jet, eq, f"tab_{k}")), k
+    o9, rho = O.atmo_probe(JD.atmo(jet, eq, "probe_x"))
+    assert np.array_equal(o9, JD.atmo(jet, eq, "probe_out9")) and np.array_equal(rho, JD.atmo(jet, eq, "probe_rho"))
+    assert np.abs(o9[:, 6]).max() > 1e-3                       # (v in km/s: not the 1e-15 of ToyAtmo)
+    a = O.absorption_probe(JD.atmo(jet, eq, "abs_x"), JD.atmo(jet, eq, "abs_f"), 0.0, 0.3)
+    assert np.array_equal(a, JD.atmo(jet, eq, "abs_alpha"))

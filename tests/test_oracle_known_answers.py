@@ -76,3 +76,21 @@ def test_hamiltonian_residuals_at_arrivals_polar():
     n0, h0, hd0 = K.hamiltonian_residuals(H.EQ_GLOBAL, rec[:, :1], lambda x: O.atmo_probe(x)[0], c_src)
     print(f"{n} arrivals: |H| <= {h:.2e}; first legs ({n0}): |H_deriv| / |mu| <= {hd0:.2e}, all legs {hd:.2e}")
     assert n >= 100 and h < 1e-4 and hd0 < 2e-2
+
+
+@pytest.mark.parametrize("tag", ["a_amp1", "b_amp1"])
+def test_hamiltonian_residuals_at_arrivals_jet(tag):
+    """the same self-checks on the oracle's records of the jet fans (tests/golden/jet_small.npz; tests/test_oracle_golden.py holds the oracle to them bit for
+    bit): meridional wind of tens of m/s in nu . wind and nu . wind'.  Fan (b) starts INSIDE the wind: the constant of GeoAc_EvalHamiltonian, c(source) / c, is
+    the right one there too - the initial slowness is n / (1 + n . wind / c0) (EquationSets.Global.cpp:82-108), so |nu| + nu . wind / c = 1 at the source.
+    The mid-latitude bounds; the oracle measures |H| 3.9e-6 / 5.3e-6 and, on the first legs, 1.7e-2 / 1.0e-2 (fan a / fan b)."""
+    import jet_data as JD
+    g = np.load(JD.FIXTURE)
+    O = H.Oracle(H.EQ_GLOBAL, met=JD.JET, fmt=JD.FMT)
+    rec, _, _ = JD.table(g, H.EQ_GLOBAL, tag)              # (the oracle's own bits: test_oracle_golden.py::test_jet_fan_records_bitexact)
+    z = JD.fan(g, tag)[2]
+    c_src = O.atmo_probe(np.array([K.R_EARTH + z]))[0][0, 0]
+    n, h, hd = K.hamiltonian_residuals(H.EQ_GLOBAL, rec, lambda x: O.atmo_probe(x)[0], c_src)
+    n0, h0, hd0 = K.hamiltonian_residuals(H.EQ_GLOBAL, rec[:, :1], lambda x: O.atmo_probe(x)[0], c_src)
+    print(f"{tag}: {n} arrivals: |H| <= {h:.2e}; first legs ({n0}): |H_deriv| / |mu| <= {hd0:.2e}, all legs {hd:.2e}")
+    assert n >= 60 and n0 >= 20 and h < 1e-4 and hd0 < 2e-2

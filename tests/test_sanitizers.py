@@ -7,6 +7,7 @@ import subprocess
 import pytest
 
 import harness as H
+import jet_data as JD
 import rngdep_data as RD
 
 SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
@@ -18,7 +19,7 @@ def test_host_helpers_under_asan_ubsan(tmp_path):
     subprocess.check_call(["g++", "-std=c++17"] + SAN + ["-o", exe, os.path.join(H.ROOT, "tests", "sanitize", "san_host_driver.cpp"),
                                                          os.path.join(H.ROOT, "geoac_amd", "csrc", "geoac_host.cpp")])
     grid = RD.write_grid(str(tmp_path / "g"), short_paths=False)
-    r = subprocess.run([exe, H.TOYATMO, *grid], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
+    r = subprocess.run([exe, H.TOYATMO, *grid, JD.JET], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert r.returncode == 0 and b"san_host_driver ok" in r.stdout, r.stdout.decode()[-3000:]
 
 
