@@ -5,6 +5,8 @@ by oracle/Makefile from /root/reference).  Run here only (the reference does not
     python tests/golden/make_golden.py polar                            # global_polar.npz (3 minutes on one core)
     python tests/golden/make_golden.py globalrd_polar                   # globalrd_polar.npz (2 minutes)
     python tests/golden/make_golden.py jet                              # jet_small.npz: the stratified sets on tests/golden/JetAtmo.met (`zuvwTdp`; 4 minutes on three cores)
+    python tests/golden/make_golden.py ragged3d                         # rngdep_ragged.npz (the columns) + rngdep_ragged_3drd.npz: the ragged 7 x 4 jet grid (3 minutes on six cores)
+    python tests/golden/make_golden.py raggedglobal                     # rngdep_ragged.npz + rngdep_ragged_globalrd.npz
 
 The fixtures are data: launch angles + configuration in, full-precision arrival records / samples /
 probe values out.  tests/test_oracle_golden.py pins the plain-C oracle to them bit for bit;
@@ -122,7 +124,8 @@ def main_rngdep():
             if amp == 1 and mode == 3:
                 sel = np.arange(0, len(smp), 4)
                 out[f"smp_idx_{tag}"] = sel; out[f"smp_{tag}"] = smp[sel]
-    # off-centre source, raised ground (enters the wind taper in this main), tighter box
+    # off-centre elevated source, other frequency and absorption scale, tighter box.  The ground stays at 0 (this main tapers the winds around z_grnd when it LOADS:
+    # a raised ground in the Cartesian grid set is main_ragged's, below)
     cfg = H.make_cfg(eq, bounces=2, calc_amp=True, mode=0, src=(120.0, -60.0, 1.0), freq=0.4, tweak_abs=0.6,
                      xy_limits=(-700.0, 900.0, -600.0, 700.0))
     steps, rec, _, _ = R.fan(cfg, th, ph)
@@ -398,8 +401,174 @@ def main_jet():
     print("jet ->", path, os.path.getsize(path) // 1024, "KiB")
 
 
+# ---- both range-dependent sets on the ragged 7 x 4 jet grid (rngdep_data.write_grid_ragged; tests/test_gpu_rngdep.py, test_gpu_globalrd.py, test_gpu_probes.py,
+#      test_host_grid.py, test_oracle_rngdep.py, test_oracle_globalrd.py) ----
+# nx != ny, unequal node spacing on both horizontal axes (neighbouring cells 350 | 180 km, 1.5 | 3.5 degrees), irregular heights with six 3.3 m segments
+# next to segments of 71 .. 379 m (rngdep_data.ragged_heights), winds of +-50 m/s with a meridional part that changes sign, a raised ground (z_grnd = 0.3: the Cartesian main tapers the winds around
+# it when it LOADS, the spherical -prop loads with 0 and raises the ground afterwards).  Fan a: from the ground, off every node.  Fan b: from 12 km - wind at the source -
+# with rays launched below the horizontal, freq = 10 and tweak_abs = 0.6; b_f001 the same at 0.01 Hz.  Two bounces: about every second leg leaves the grid (BROKE, with
+# an exact step count).
+RAGGED_SRC = {H.EQ_3D_RNGDEP: {"a": (60.0, -40.0, 0.0), "b": (-100.0, 50.0, 12.0)}, H.EQ_GLOBAL_RNGDEP: {"a": (0.0, 30.7, 2.2), "b": (12.0, 30.0, -1.0)}}
+RAGGED_TH = {"a": [4.0, 9.0, 15.0, 21.0, 27.0], "b": [-12.0, -3.0, 8.0, 22.0, 38.0]}
+RAGGED_AZ = {"a": [-70.0, 35.0, 150.0], "b": [-100.0, -25.0, 40.0, 115.0, 170.0]}
+RAGGED_ZG = 0.3
+# Rays left out of a fan (theta, azimuth): they fail the conditioning assertion of main_ragged on the compiled reference (at most one ray in ten of a fan).
+#   globalrd a (15, -70): theta (1 + 1e-12) moves the launch-angle derivatives of its second arrival by 9.3e-6 in the reference itself (STATE, amplitudes on; every
+#   other field and the amplitude-less run stay below 2e-8) - the ray turns inside one of the 3.3 m segments, where quirk Q12a multiplies the slopes
+RAGGED_DROPPED = {H.EQ_3D_RNGDEP: {"a": [], "b": []}, H.EQ_GLOBAL_RNGDEP: {"a": [(15.0, -70.0)], "b": []}}
+
+
+def ragged_fan(eq, name):
+    rays = [(t, a) for a in RAGGED_AZ[name] for t in RAGGED_TH[name] if (t, a) not in RAGGED_DROPPED[eq][name]]
+    assert len(rays) <= 30 and 10 * (len(RAGGED_AZ[name]) * len(RAGGED_TH[name]) - len(rays)) <= len(RAGGED_AZ[name]) * len(RAGGED_TH[name])
+    return np.array([r[0] for r in rays]), np.array([r[1] for r in rays])
+
+
+def _ragged_load(eq, grid):
+    """reference and oracle with the grid loaded as the set's main loads it"""
+    zl = RAGGED_ZG if eq == H.EQ_3D_RNGDEP else 0.0
+    R = H.RefShim(eq, grid=grid, z_grnd=zl)
+    O = H.Oracle(eq, met=None); O.load_grid(*grid, z_grnd=zl)
+    return R, O
+
+
+def _ragged_probe_points(eq):
+    """400 points in the set's own coordinates (a, b: the horizontal axes, z: height above the first node).  The first NODE points sit on nodes of all three axes:
+    first and last node of each axis, the nodes on either side of the widest-to-narrowest pair of neighbouring cells, the nodes of a 3 m segment; then 60 points in and
+    on the 3 m segments, 40 a third of a cell beyond every edge, and random ones"""
+    import rngdep_data as RD
+    glob = eq == H.EQ_GLOBAL_RNGDEP
+    na, nb = RD.ragged_nodes(glob)
+    zn = np.load(RD.RAGGED_NPZ)["z"]
+    short = np.flatnonzero(np.diff(zn) < RD.RAGGED_SHORT)
+    rng = np.random.default_rng(2027 + int(glob))
+    n = 400
+    a = rng.uniform(na[0], na[-1], n); b = rng.uniform(nb[0], nb[-1], n); z = rng.uniform(-1.0, zn[-1] + 1.0, n)
+    ia = [0, 6, 1, 2, 3, 2, 5, 4, 0, 6, 3, 1]           # (cells 350 | 180 km and 1.5 | 3.5 degrees: nodes 1, 2, 3)
+    ib = [0, 3, 1, 2, 1, 2, 0, 3, 3, 0, 2, 1]
+    iz = [0, len(zn) - 1, 7, 1, short[0], short[0] + 1, short[-1], short[-1] + 1, 100, len(zn) - 2, 200, short[len(short) // 2]]
+    a[:12] = na[ia]; b[:12] = nb[ib]; z[:12] = zn[iz]
+    k = short[np.arange(20) % len(short)]
+    z[12:72] = np.concatenate([zn[k[:20]], zn[k[:20] + 1], zn[k[:20]] + np.diff(zn)[k[:20]] * rng.uniform(0.05, 0.95, 20)])
+    da, db = np.diff(na), np.diff(nb)
+    a[72:82] = na[0] - da[0] / 3.0; a[82:92] = na[-1] + da[-1] / 3.0; b[92:102] = nb[0] - db[0] / 3.0; b[102:112] = nb[-1] + db[-1] / 3.0
+    a[92:97] = na[0] - da[0] / 3.0; a[102:107] = na[-1] + da[-1] / 3.0          # (corners: beyond two edges at once)
+    return a, b, z
+
+
+RAGGED_NODE_POINTS = 12
+
+
+def _ragged_probe(R, O, eq):
+    a, b, z = _ragged_probe_points(eq)
+    if eq == H.EQ_GLOBAL_RNGDEP:
+        args = (6370.0 + z, np.radians(a), np.radians(b))
+        names = ("probe_r", "probe_lat", "probe_lon")
+    else:
+        args = (a, b, z)
+        names = ("probe_x", "probe_y", "probe_z")
+    o30, a8 = R.grid_probe(*args)
+    oo30, oa8 = O.grid_probe(*args)
+    assert np.array_equal(oo30, o30) and np.array_equal(oa8, a8), "the oracle's interpolant differs from the compiled reference's"
+    assert np.isfinite(o30).all() and np.isfinite(a8).all()
+    out = dict(zip(names, args))
+    out.update(probe_out30=o30, probe_api8=a8, probe_node_points=np.int64(RAGGED_NODE_POINTS))
+    return out
+
+
+def _ragged_table(job):
+    """one table's share of a ragged fixture (a process of its own: the reference takes 25 .. 45 s per 20 rays): (tag, arrays, printed line, failures)"""
+    from parity import field_errors
+    eq, grid, tag = job
+    if tag == "probe":
+        R, O = _ragged_load(eq, grid)
+        return tag, _ragged_probe(R, O, eq), "", []
+    import rngdep_data as RD
+    fan, kw = RD.RAGGED_TABLES[tag]
+    th, ph = ragged_fan(eq, fan)
+    R, O = _ragged_load(eq, grid)
+    cfg = H.make_cfg(eq, src=RAGGED_SRC[eq][fan], z_grnd=RAGGED_ZG, **kw)
+    steps, rec, _, _ = R.fan(cfg, th, ph)
+    so, ro, _, _ = O.fan(cfg, th, ph)
+    assert so == steps and np.array_equal(ro, rec), f"{tag}: the oracle's records differ from the compiled reference's"
+    sp, rp, _, _ = R.fan(cfg, th * (1.0 + POLAR_SENS_EPS), ph)
+    failures = []
+    moved = np.flatnonzero((rp[..., :3] != rec[..., :3]).any(axis=(1, 2)))
+    E = (18 if kw["calc_amp"] else 6)
+    hidx = 2 if eq == H.EQ_3D_RNGDEP else 0
+    fe = field_errors(rp, rec, E, hidx)
+    fields = sorted(fe)
+    sens = np.stack([fe[f] for f in fields], axis=-1)
+    worst = {f: float(np.nanmax(fe[f])) for f in fields}
+    per_ray = np.nanmax(np.nan_to_num(sens), axis=(1, 2))
+    if len(moved):
+        failures.append(f"{tag}: VALID / STEPS / BROKE move with theta (1 + {POLAR_SENS_EPS:g}) on rays {[(th[i], ph[i]) for i in moved]}")
+    if not 4.0 * np.nanmax(sens) <= 1e-6:
+        failures.append(f"{tag}: the reference itself is ill-conditioned on rays {[(th[i], ph[i], float(per_ray[i])) for i in np.flatnonzero(per_ray > 2.5e-7)]}: {worst}")
+    valid = rec[..., H.REC["VALID"]] > 0
+    line = (f"{H.EQ_NAMES[eq]} {tag}: {steps} steps, {int(valid.sum())} of {valid.size} legs VALID ({int(valid[th < 0].sum())} of rays launched downwards), "
+            f"{int((rec[..., H.REC['BROKE']] > 0).sum())} BROKE, longest leg {int(rec[..., H.REC['STEPS']].max())} steps; worst sensitivity " + ", ".join(f"{f} {v:.1e}" for f, v in worst.items()))
+    out = {f"{tag}_rec": rec, f"{tag}_steps": np.int64(steps), f"{tag}_sens": sens.astype(np.float32), f"{tag}_sens_fields": np.array(fields)}
+    return tag, out, line, failures
+
+
+def ragged_cells(eq, rec):
+    """the grid cells (ia, ib) the arrivals of a record table land in"""
+    import rngdep_data as RD
+    glob = eq == H.EQ_GLOBAL_RNGDEP
+    na, nb = RD.ragged_nodes(glob)
+    st = rec[..., H.REC["STATE"]:H.REC["STATE"] + 3][rec[..., H.REC["VALID"]] > 0]
+    pa, pb = (np.degrees(st[:, 1]), np.degrees(st[:, 2])) if glob else (st[:, 0], st[:, 1])
+    return set(zip(np.searchsorted(na, pa).tolist(), np.searchsorted(nb, pb).tolist()))
+
+
+def main_ragged(eq):
+    """rngdep_ragged_<set>.npz: per table the compiled reference's records, step total and `sens` (as main_polar stores it: 4 x sens <= 1e-6 asserted for every field of
+    every arrival, VALID / STEPS / BROKE asserted unchanged under theta (1 + 1e-12)), the oracle asserted equal bit for bit; Eval_Spline_AllOrder2 and the scalar API at
+    400 points; node arrays and sources.  b_f001 is stored as its ATTEN column: every other column is asserted equal to b_amp1's."""
+    import tempfile
+    import rngdep_data as RD
+    from concurrent.futures import ProcessPoolExecutor
+    glob = eq == H.EQ_GLOBAL_RNGDEP
+    sname = H.EQ_NAMES[eq]
+    RD.save_grid_ragged_npz()
+    grid = RD.write_grid_ragged(os.path.join(tempfile.gettempdir(), "rg" if glob else "rc"), glob)
+    na, nb = RD.ragged_nodes(glob)
+    out = {"nodes_a": na, "nodes_b": nb, "z_grnd": np.float64(RAGGED_ZG), "sens_eps": np.float64(POLAR_SENS_EPS)}
+    for fan in ("a", "b"):
+        th, ph = ragged_fan(eq, fan)
+        out[f"{fan}_theta"] = th; out[f"{fan}_phi"] = ph; out[f"{fan}_src"] = np.array(RAGGED_SRC[eq][fan])
+    jobs = [(eq, grid, tag) for tag in list(RD.RAGGED_TABLES) + ["probe"]]
+    with ProcessPoolExecutor(max_workers=len(jobs)) as pool:
+        res = list(pool.map(_ragged_table, jobs))
+    failures = []
+    for tag, arrays, line, fails in res:
+        out.update(arrays)
+        failures += fails
+        if line:
+            print(line)
+    assert not failures, "\n".join(failures)
+    other = np.arange(H.REC_STRIDE) != H.REC["ATTEN"]
+    assert np.array_equal(out["b_f001_rec"][..., other], out["b_amp1_rec"][..., other]), "freq changes more than ATTEN"
+    assert not np.array_equal(out["b_f001_rec"][..., H.REC["ATTEN"]], out["b_amp1_rec"][..., H.REC["ATTEN"]])
+    out["b_f001_atten"] = out.pop("b_f001_rec")[..., H.REC["ATTEN"]]
+    # what the fans must reach
+    rec = np.concatenate([out["a_amp1_rec"], out["b_amp1_rec"]])
+    n_valid = int((rec[..., H.REC["VALID"]] > 0).sum()); n_broke = int((rec[..., H.REC["BROKE"]] > 0).sum())
+    longest = int(rec[..., H.REC["STEPS"]].max()); cells = ragged_cells(eq, rec)
+    print(f"{sname}: fans a + b (amplitudes on): {n_valid} VALID legs, {n_broke} BROKE, longest leg {longest} steps, arrivals in {len(cells)} cells {sorted(cells)}")
+    assert n_valid >= 15 and n_broke >= 10 and longest > 15000 and len(cells) >= 6
+    path = os.path.join(OUT, f"rngdep_ragged_{sname}.npz")
+    np.savez_compressed(path, **out)
+    print(f"ragged {sname} ->", path, os.path.getsize(path) // 1024, "KiB;", os.path.getsize(RD.RAGGED_NPZ) // 1024, "KiB grid")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "jet":
+    if len(sys.argv) > 1 and sys.argv[1] == "ragged3d":
+        main_ragged(H.EQ_3D_RNGDEP)
+    elif len(sys.argv) > 1 and sys.argv[1] == "raggedglobal":
+        main_ragged(H.EQ_GLOBAL_RNGDEP)
+    elif len(sys.argv) > 1 and sys.argv[1] == "jet":
         main_jet()
     elif len(sys.argv) > 1 and sys.argv[1] == "polar":
         main_polar()

@@ -135,3 +135,107 @@ def write_grid_global(dirpath, short_paths=True, centre_lat=CENTRE_LAT, lat_step
     with open(loclon, "w") as fh:
         fh.write("".join(f"{y:.10g}\n" for y in lon_nodes))
     return prefix, loclat, loclon
+
+
+# ---- a ragged 7 x 4 grid for both sets: unequal node spacing on both horizontal axes (nx != ny), irregular heights, a jet with meridional wind.
+#      tests/golden/rngdep_ragged.npz holds the columns (make_golden.py ragged3d / raggedglobal; fixtures rngdep_ragged_{3drd,globalrd}.npz).  The columns are
+#      JetAtmo.met's (tests/jet_data.py) on a subset of its own irregular nodes, modulated across the grid by the node's position a, b in [-0.5, 0.5] along the
+#      Cartesian axes; the spherical grid holds the same columns on its own nodes.  File index n = i * 4 + j.
+#      Heights (ragged_heights): every third node (segments of 0.2 .. 0.8 km, neighbours up to 1 : 10), and around every ninth of the profile's 3.3 m segments all
+#      eight of its nodes: 328 heights, six 3.3 m segments whose neighbours are 71 .. 379 m long.  No more and no closer: the spherical reference's slope systems (quirk Q12a)
+#      take the right-hand side of a node from the segment ABOVE it on both sides, which multiplies the slope there by about hr / hl.  With both ends of a 3.3 m
+#      segment put back between two 0.6 km ones (1 : 200) the reference's own rays turn chaotic - theta (1 + 1e-12) moved its arrivals by 1e-3 and its step counts -
+#      and no arithmetic but its own bit pattern follows it; with the profile's own nodes around a short segment its answer stays below 1e-7 on all but one ray. ----
+RAGGED_X = np.array([-900.0, -650.0, -300.0, -120.0, 150.0, 520.0, 1000.0])
+RAGGED_Y = np.array([-700.0, -250.0, 180.0, 800.0])
+RAGGED_LAT = np.array([24.0, 26.5, 28.0, 31.5, 33.0, 36.0, 38.5])
+RAGGED_LON = np.array([-9.0, -3.5, 1.0, 8.0])
+RAGGED_NPZ = os.path.join(H.GOLDEN_DIR, "rngdep_ragged.npz")
+RAGGED_SHORT = 0.03           # km: segments below this count as short
+
+
+def ragged_heights(zj):
+    """indices of the JetAtmo nodes the ragged grid keeps"""
+    keep = set(range(0, len(zj), 3)) | {len(zj) - 1}
+    short = np.flatnonzero(np.diff(zj) < RAGGED_SHORT)
+    for k in short[::9]:
+        keep |= set(range(int(k) - 3, int(k) + 5))
+    return np.array(sorted(keep))
+
+
+def grid_columns_ragged():
+    """z [nz], T, u, v, rho [7][4][nz], p [nz] (raw .met units)"""
+    import jet_data as JD
+    c = JD.load_columns()
+    k = ragged_heights(c["z"])
+    z, T0, u0, v0, rho0, p = (c[q][k] for q in ("z", "T", "u", "v", "rho", "p"))
+    nx, ny = len(RAGGED_X), len(RAGGED_Y)
+    T = np.zeros((nx, ny, len(z))); u = np.zeros_like(T); v = np.zeros_like(T); rho = np.zeros_like(T)
+    for i in range(nx):
+        for j in range(ny):
+            a = (RAGGED_X[i] - RAGGED_X[0]) / (RAGGED_X[-1] - RAGGED_X[0]) - 0.5
+            b = (RAGGED_Y[j] - RAGGED_Y[0]) / (RAGGED_Y[-1] - RAGGED_Y[0]) - 0.5
+            T[i, j] = T0 * (1.0 + 0.02 * np.sin(2.3 * a + 1.1 * b) * np.exp(-((z - 50.0) / 20.0) ** 2))
+            u[i, j] = u0 * (1.0 + 0.3 * a) + 6.0 * np.sin(3.0 * b)
+            v[i, j] = v0 * (1.0 - 0.4 * b) + 5.0 * np.cos(2.5 * a) * np.exp(-z / 60.0)
+            rho[i, j] = rho0 * (1.0 + 0.01 * np.cos(1.7 * a - 2.2 * b))
+    return z, T, u, v, rho, p
+
+
+def save_grid_ragged_npz():
+    z, T, u, v, rho, p = grid_columns_ragged()
+    np.savez_compressed(RAGGED_NPZ, z=z, T=T, u=u, v=v, rho=rho, p=p, x=RAGGED_X, y=RAGGED_Y, lat=RAGGED_LAT, lon=RAGGED_LON)
+
+
+def ragged_nodes(glob):
+    return (RAGGED_LAT, RAGGED_LON) if glob else (RAGGED_X, RAGGED_Y)
+
+
+def write_grid_ragged(dirpath, glob, short_paths=True):
+    """writes r<n>.met (`zTuvdp`: the reference's range-dependent loaders take six-column files only) and the two node files (km, or degrees for the
+    spherical set); returns (prefix, loc_a, loc_b)"""
+    os.makedirs(dirpath, exist_ok=True)
+    g = np.load(RAGGED_NPZ)
+    z, T, u, v, rho, p = g["z"], g["T"], g["u"], g["v"], g["rho"], g["p"]
+    na, nb = ragged_nodes(glob)
+    prefix = os.path.join(dirpath, "r")
+    assert len(prefix) < 40 or not short_paths
+    for i in range(len(na)):
+        for j in range(len(nb)):
+            with open(f"{prefix}{i * len(nb) + j}.met", "w") as fh:
+                for k in range(len(z)):
+                    fh.write(f"{z[k]:.10g} {T[i, j, k]:.12g} {u[i, j, k]:.12g} {v[i, j, k]:.12g} {rho[i, j, k]:.12g} {p[k]:.10g}\n")
+    loc_a, loc_b = os.path.join(dirpath, "loc_a.dat"), os.path.join(dirpath, "loc_b.dat")
+    with open(loc_a, "w") as fh:
+        fh.write("".join(f"{x:.10g}\n" for x in na))
+    with open(loc_b, "w") as fh:
+        fh.write("".join(f"{y:.10g}\n" for y in nb))
+    return prefix, loc_a, loc_b
+
+
+# ---- tests/golden/rngdep_ragged_{3drd,globalrd}.npz (make_golden.py ragged3d / raggedglobal): what the tables were made with, and how to read them ----
+RAGGED_ZG = 0.3               # z_grnd of every table; the Cartesian main also LOADS with it (wind taper), the spherical -prop loads with 0
+# table -> (fan, parameters besides src and z_grnd); fan a: ground source off every node, fan b: source at 12 km, rays below the horizontal included
+RAGGED_TABLES = {"a_amp1": ("a", dict(bounces=2, calc_amp=1)), "a_amp0": ("a", dict(bounces=2, calc_amp=0)),
+                 "b_amp1": ("b", dict(bounces=2, calc_amp=1, freq=10.0, tweak_abs=0.6)), "b_amp0": ("b", dict(bounces=2, calc_amp=0, freq=10.0, tweak_abs=0.6)),
+                 "b_f001": ("b", dict(bounces=2, calc_amp=1, freq=0.01, tweak_abs=0.6))}
+
+
+def ragged_fixture(glob):
+    return np.load(os.path.join(H.GOLDEN_DIR, f"rngdep_ragged_{'globalrd' if glob else '3drd'}.npz"))
+
+
+def ragged_load_z_grnd(glob):
+    return 0.0 if glob else RAGGED_ZG
+
+
+def ragged_table(g, tag):
+    """(theta, phi, parameters, records, step total, sens) of a table.  b_f001 is stored as its ATTEN column: the generator asserted every other column equal to b_amp1's"""
+    fan, kw = RAGGED_TABLES[tag]
+    if f"{tag}_rec" in g.files:
+        rec = g[f"{tag}_rec"]
+    else:
+        rec = g["b_amp1_rec"].copy()
+        rec[..., H.REC["ATTEN"]] = g[f"{tag}_atten"]
+    params = dict(kw, src=tuple(g[f"{fan}_src"]), z_grnd=float(g["z_grnd"]))
+    return g[f"{fan}_theta"], g[f"{fan}_phi"], params, rec, int(g[f"{tag}_steps"]), g[f"{tag}_sens"]

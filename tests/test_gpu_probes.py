@@ -81,12 +81,13 @@ def test_cartesian_grid_interpolant_vs_reference(coop, tmp_path):
     assert e.max() <= RTOL and ea.max() <= RTOL
 
 
-def _spherical_grid_interpolant_vs_reference(coop, tmp_path, fixture, grid_kw, src, tag):
+def _spherical_grid_interpolant_vs_reference(coop, tmp_path, fixture, grid_kw, src, tag, ragged=False):
     import geoac_amd as G
     import rngdep_data as RD
-    g = np.load(f"{H.GOLDEN_DIR}/{fixture}")
+    g = RD.ragged_fixture(True) if ragged else np.load(f"{H.GOLDEN_DIR}/{fixture}")
+    nn = int(g["probe_node_points"]) if ragged else 6              # the leading probe points that sit on nodes of all three axes
     ctx = G.FanContext(G.EQ_GLOBAL_RNGDEP, device=0)
-    ctx.load_grid(*RD.write_grid_global(str(tmp_path), short_paths=False, **grid_kw))
+    ctx.load_grid(*(RD.write_grid_ragged(str(tmp_path), True, short_paths=False) if ragged else RD.write_grid_global(str(tmp_path), short_paths=False, **grid_kw)))
     ctx.set_params(bounces=0, calc_amp=1, mode=0, src=src)
     ctx.run(np.array([20.0]), np.array([-90.0]))
     o30, a7 = ctx.probe_grid(g["probe_lat"], g["probe_lon"], g["probe_r"], coop=coop)
@@ -97,8 +98,8 @@ def _spherical_grid_interpolant_vs_reference(coop, tmp_path, fixture, grid_kw, s
     # node depends on the history of its search cursor (Q13) - those six points are compared on value and gradient only
     want = g["probe_out30"]
     second = np.array([q >= 4 for q in range(10)] * 3)
-    e = _colwise(got[6:], want[6:], field_scale=_field_scales(want))
-    e_nodes = _colwise(got[:6][:, ~second], want[:6][:, ~second], field_scale=_field_scales(want)[~second])
+    e = _colwise(got[nn:], want[nn:], field_scale=_field_scales(want))
+    e_nodes = _colwise(got[:nn][:, ~second], want[:nn][:, ~second], field_scale=_field_scales(want)[~second])
     e = np.concatenate([e, e_nodes])
     ea = _colwise(a7, g["probe_api8"][:, :7])
     print(tag + " coop" if coop else tag, "AllOrder2 max rel err", f"{e.max():.1e}", "scalar API", [f"{v:.1e}" for v in ea])
@@ -127,6 +128,33 @@ def test_polar_grid_interpolant_vs_reference(coop, tmp_path, time_limit):
     tests/golden/globalrd_polar.npz): points up to 89.95 N, beyond the last row, and beyond the first and last column"""
     import rngdep_data as RD
     _spherical_grid_interpolant_vs_reference(coop, tmp_path, "globalrd_polar.npz", RD.POLAR_GRID, (0.0, 86.0, 0.0), "globalrd polar")
+
+
+@pytest.mark.parametrize("coop", [False, True])
+def test_ragged_spherical_grid_interpolant_vs_reference(coop, tmp_path, time_limit):
+    """the same 30 values and scalar API on the ragged 7 x 4 jet grid (rngdep_data.write_grid_ragged; reference values in tests/golden/rngdep_ragged_globalrd.npz):
+    nx != ny, unequal spacing on all three axes - the slope systems of quirk Q12a have a right-hand side there -, points on first, last and the most unequal
+    neighbouring nodes, inside and on the 3.3 m height segments, and a third of a cell beyond every edge"""
+    _spherical_grid_interpolant_vs_reference(coop, tmp_path, None, None, (0.0, 30.7, 2.2), "globalrd ragged", ragged=True)
+
+
+@pytest.mark.parametrize("coop", [False, True])
+def test_ragged_cartesian_grid_interpolant_vs_reference(coop, tmp_path, time_limit):
+    """the Cartesian twin (tests/golden/rngdep_ragged_3drd.npz), loaded with z_grnd = 0.3 as the set's main loads: the wind taper around a raised ground is part of
+    what is compared.  The leading points sit on nodes of all three axes; this set's second derivatives are judged there too, as on the 5 x 5 grid"""
+    import geoac_amd as G
+    import rngdep_data as RD
+    g = RD.ragged_fixture(False)
+    ctx = G.FanContext(G.EQ_3D_RNGDEP, device=0)
+    ctx.load_grid(*RD.write_grid_ragged(str(tmp_path), False, short_paths=False), z_grnd=RD.ragged_load_z_grnd(False))
+    ctx.set_params(bounces=0, calc_amp=1, mode=0, src=(60.0, -40.0, 0.0), z_grnd=float(g["z_grnd"]))
+    ctx.run(np.array([20.0]), np.array([-90.0]))
+    o30, a7 = ctx.probe_grid(g["probe_x"], g["probe_y"], g["probe_z"], coop=coop)
+    e = _colwise(o30, g["probe_out30"], field_scale=_field_scales(g["probe_out30"]))
+    ea = _colwise(a7, g["probe_api8"][:, :7])
+    print("3drd ragged coop" if coop else "3drd ragged", "AllOrder2 max rel err", f"{e.max():.1e}", "scalar API", [f"{v:.1e}" for v in ea])
+    print("   per column", [f"{v:.0e}" for v in e])
+    assert e.max() <= RTOL and ea.max() <= RTOL
 
 
 def test_cooperative_and_per_lane_gathers_give_the_same_bits_on_the_polar_grid(tmp_path, time_limit):

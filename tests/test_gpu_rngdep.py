@@ -6,7 +6,7 @@ import pytest
 import harness as H
 from geoac_amd.api import DEFAULT_OPTIONS as OPT      # launch-plan options of the contexts the tests create (geoac_set_option)
 import rngdep_data as RD
-from parity import compare_records, max_rel_errors
+from parity import compare_records, field_errors, max_rel_errors
 
 pytestmark = pytest.mark.gpu
 EQ = H.EQ_3D_RNGDEP
@@ -124,3 +124,99 @@ def test_tiled_slot_order_gives_the_inclination_orders_bits(grid, monkeypatch):
         out[name] = ctx.run(th, ph)
     assert out["tile"][1] == out["incl"][1] == out["caller"][1]
     assert np.array_equal(out["tile"][0], out["incl"][0]) and np.array_equal(out["tile"][0], out["caller"][0])
+
+
+# ---- the ragged 7 x 4 jet grid (rngdep_data.write_grid_ragged): nx != ny, unequal node spacing on all three axes, 3.3 m height segments, winds of +-50 m/s with a
+#      meridional part, raised ground, sources on the ground and inside the jet at 12 km, rays launched below the horizontal, 10 Hz and 0.01 Hz; fixture
+#      tests/golden/rngdep_ragged_3drd.npz from the compiled reference (make_golden.py ragged3d) ----
+STEP_LIMIT_S = 120
+
+
+@pytest.fixture
+def time_limit():
+    import faulthandler
+    faulthandler.dump_traceback_later(STEP_LIMIT_S, exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+# launch-plan options -> every kernel the shipped library can select for the amplitudes-on table of fan b (25 rays)
+RAGGED_VARIANTS = {
+    "default": {},                                                              # eight lanes per ray (Eq3DRngDepOct)
+    "oct0": {"OCT": "0"},                                                      # four lanes per ray, as the plan picks them
+    "lanes4": {"GRID_LANES": "4"},
+    "lanes1": {"GRID_LANES": "1"},
+    "coop": {"GRID_LANES": "1", "SPREAD": "1", "GRID_COOP": "1"},               # one lane per ray without lane thinning, wave-cooperative gather: as a large fan runs
+    "dense": {"GRID_LANES": "1", "SPREAD": "1", "GRID_COOP": "0"},              # the same launch with per-lane gathers
+    "coop+sub": {"GRID_LANES": "1", "SPREAD": "1", "GRID_COOP": "1", "SUB_MIN_WAVES": "0", "SUB_EPOCHS": "4", "S_ROWS": "512"},     # the plan of saturated fans
+    "tile0": {"GRID_LANES": "1", "TILE": "0"},                                  # slot order: by inclination ...
+    "sort0": {"GRID_LANES": "1", "SORT": "0"},                                  # ... and the caller's
+}
+# variants that perform the same operations on the same operands (the tests above state it for the 5 x 5 grid): the same records bit for bit
+RAGGED_SAME_BITS = [("default", "oct0", "lanes4"), ("lanes1", "tile0", "sort0")]
+_ragged_runs = {}
+
+
+@pytest.fixture(scope="module")
+def gold_ragged():
+    return RD.ragged_fixture(False)
+
+
+@pytest.fixture(scope="module")
+def grid_ragged(tmp_path_factory):
+    return RD.write_grid_ragged(str(tmp_path_factory.mktemp("rr")), False, short_paths=False)
+
+
+def _ragged_run(grid, g, tag, opts):
+    from geoac_amd.api import options
+    import geoac_amd as G
+    th, ph, params, want, steps_want, sens = RD.ragged_table(g, tag)
+    with options(**opts):
+        ctx = G.FanContext(EQ, device=0)
+        ctx.load_grid(*grid, z_grnd=RD.ragged_load_z_grnd(False))          # this set's main tapers the winds around z_grnd when it loads
+        ctx.set_params(mode=0, **params)
+        rec, steps = ctx.run(th, ph)
+        rec = rec.copy(); ctx.close()
+    return rec, steps, want, steps_want, sens
+
+
+def _ragged_variant(grid, g, name):
+    if name not in _ragged_runs:
+        _ragged_runs[name] = _ragged_run(grid, g, "b_amp1", RAGGED_VARIANTS[name])
+    return _ragged_runs[name]
+
+
+def _ragged_check(tag, what, rec, steps, want, steps_want, E):
+    fe = field_errors(rec, want, E, 2)
+    print(f"3drd ragged {tag} {what}: worst error per field: " + ", ".join(f"{f} {np.nanmax(fe[f]):.2e}" for f in sorted(fe)), max_rel_errors(rec, want, E, 2))
+    assert steps == steps_want
+    compare_records(rec, want, E=E, hidx=2)
+
+
+@pytest.mark.parametrize("tag", list(RD.RAGGED_TABLES))
+def test_ragged_fan_vs_golden(gold_ragged, grid_ragged, tag, time_limit):
+    """every table of the fixture under the plan's own kernel: the step total and VALID / STEPS / BROKE of every leg exact, every field compare_records judges within
+    1e-6.  The reference's own answer to theta (1 + 1e-12) is in the fixture for every field of every arrival: no exemptions (the generator names the rays it left out)."""
+    g = gold_ragged
+    rec, steps, want, steps_want, sens = _ragged_run(grid_ragged, g, tag, {})
+    assert 4.0 * np.nanmax(sens) <= 1e-6
+    if tag == "b_amp1":
+        both = np.concatenate([want, RD.ragged_table(g, "a_amp1")[3]])
+        assert (both[..., H.REC["VALID"]] > 0).sum() >= 15 and (both[..., H.REC["BROKE"]] > 0).sum() >= 10 and both[..., H.REC["STEPS"]].max() > 15000
+        assert (want[g["b_theta"] < 0][..., H.REC["VALID"]] > 0).any()
+    _ragged_check(tag, "default", rec, steps, want, steps_want, 18 if RD.RAGGED_TABLES[tag][1]["calc_amp"] else 6)
+
+
+@pytest.mark.parametrize("variant", list(RAGGED_VARIANTS))
+def test_ragged_kernel_variants_vs_golden(gold_ragged, grid_ragged, variant, time_limit):
+    """fan b with amplitudes (from 12 km inside the jet, 10 Hz, raised ground) under every kernel the shipped library can select: each against the reference's records"""
+    rec, steps, want, steps_want, _ = _ragged_variant(grid_ragged, gold_ragged, variant)
+    _ragged_check("b_amp1", variant, rec, steps, want, steps_want, 18)
+
+
+def test_ragged_variants_that_associate_alike_give_the_same_bits(gold_ragged, grid_ragged, time_limit):
+    for group in RAGGED_SAME_BITS:
+        first = _ragged_variant(grid_ragged, gold_ragged, group[0])
+        for name in group[1:]:
+            got = _ragged_variant(grid_ragged, gold_ragged, name)
+            assert got[1] == first[1] and np.array_equal(got[0].view(np.uint64), first[0].view(np.uint64)), (group[0], name)

@@ -17,7 +17,7 @@ def _p(a):
     return a.ctypes.data_as(_dp)
 
 
-def _load(eq, grid):
+def _load(eq, grid, z_grnd=0.0):
     lib = G.load_library()
     nx, ny, nz = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
     assert lib.geoac_grid_dims(grid[0].encode(), grid[1].encode(), grid[2].encode(), ctypes.byref(nx), ctypes.byref(ny), ctypes.byref(nz)) == 0
@@ -25,7 +25,7 @@ def _load(eq, grid):
     x, y, z = np.zeros(nx), np.zeros(ny), np.zeros(nz)
     F = [np.zeros((nx, ny, nz)) for _ in range(4)]
     lib.geoac_grid_load_eq.argtypes = None
-    assert lib.geoac_grid_load_eq(eq, grid[0].encode(), grid[1].encode(), grid[2].encode(), b"zTuvdp", ctypes.c_double(0.0),
+    assert lib.geoac_grid_load_eq(eq, grid[0].encode(), grid[1].encode(), grid[2].encode(), b"zTuvdp", ctypes.c_double(z_grnd),
                                   nx, ny, nz, _p(x), _p(y), _p(z), *[_p(f) for f in F]) == 0
     lib.geoac_grid_table_size.restype = ctypes.c_size_t
     tab = np.zeros(lib.geoac_grid_table_size(nx, ny, nz))
@@ -63,6 +63,22 @@ def test_spherical_grid_host_evaluator_vs_reference_probes(tmp_path):
     scale = np.abs(api[:, 2:4]).max()
     assert np.abs(ev(1, plat, plon, pr) - api[:, 2]).max() < 1e-12 * scale
     assert np.abs(ev(2, plat, plon, pr) - api[:, 3]).max() < 1e-12 * scale
+
+
+@pytest.mark.parametrize("glob", [False, True])
+def test_ragged_grid_host_evaluator_vs_reference_probes(glob, tmp_path):
+    """the same four values on the ragged 7 x 4 jet grid (rngdep_data.write_grid_ragged: nx != ny, unequal spacing on all three axes, 3.3 m height segments, points on
+    nodes, inside the short segments and a third of a cell beyond every edge), loaded as each set's main loads it (the Cartesian one with z_grnd = 0.3)"""
+    g = RD.ragged_fixture(glob)
+    ev, (a, b, _) = _load(G.EQ_GLOBAL_RNGDEP if glob else G.EQ_3D_RNGDEP, RD.write_grid_ragged(str(tmp_path), glob, short_paths=False), RD.ragged_load_z_grnd(glob))
+    assert (len(a), len(b)) == (7, 4)
+    pts = (g["probe_lat"], g["probe_lon"], g["probe_r"]) if glob else (g["probe_x"], g["probe_y"], g["probe_z"])
+    api = g["probe_api8"]
+    c = np.sqrt(0.00040187 * ev(0, *pts))
+    scale = np.abs(api[:, 2:4]).max()
+    err = (np.abs(c / api[:, 0] - 1).max(), np.abs(ev(3, *pts) / api[:, 1] - 1).max(), np.abs(ev(1, *pts) - api[:, 2]).max() / scale, np.abs(ev(2, *pts) - api[:, 3]).max() / scale)
+    print("ragged", "globalrd" if glob else "3drd", "c, rho, u, v:", ["%.1e" % e for e in err])
+    assert scale > 0.04 and max(err) < 1e-12
 
 
 def _write_grid_files(dirpath, fmt, glob):

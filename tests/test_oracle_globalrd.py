@@ -71,3 +71,27 @@ def test_default_grid_files_are_unchanged(tmp_path):
     """write_grid_global without a centre latitude writes the node files the mid-latitude fixtures were made from"""
     _, loclat, loclon = RD.write_grid_global(str(tmp_path), short_paths=False)
     assert open(loclat).read() == "25\n28\n31\n34\n37\n" and open(loclon).read() == "-8\n-4\n0\n4\n8\n"
+
+
+# ---- the ragged 7 x 4 jet grid (rngdep_data.write_grid_ragged; make_golden.py raggedglobal): loaded with z_grnd = 0 as -prop does, the ground raised afterwards ----
+@pytest.fixture(scope="module")
+def oracle_ragged(tmp_path_factory):
+    O = H.Oracle(EQ, met=None)
+    O.load_grid(*RD.write_grid_ragged(str(tmp_path_factory.mktemp("rg")), True, short_paths=False), z_grnd=RD.ragged_load_z_grnd(True))
+    return O
+
+
+def test_ragged_grid_interpolant_bitexact(oracle_ragged):
+    g = RD.ragged_fixture(True)
+    o30, a8 = oracle_ragged.grid_probe(g["probe_r"], g["probe_lat"], g["probe_lon"])
+    assert np.array_equal(o30, g["probe_out30"]) and np.array_equal(a8, g["probe_api8"])
+
+
+@pytest.mark.parametrize("tag,rows", [("b_amp1", [15, 16, 19]), ("a_amp1", [0]), ("b_amp0", [17]), ("b_f001", [4])])
+def test_ragged_fan_records_bitexact(oracle_ragged, tag, rows):
+    """six rays of the fixture's tables (rays are independent; the fixture script ran the oracle on all of them): a ray launched downwards that arrives three
+    times, legs that BREAK at the edge after one and two arrivals (one after 18 017 steps), 10 Hz and 0.01 Hz"""
+    th, ph, params, want, _, _ = RD.ragged_table(RD.ragged_fixture(True), tag)
+    steps, rec, _, _ = oracle_ragged.fan(H.make_cfg(EQ, **params), th[rows], ph[rows])
+    assert steps == int(want[rows][..., H.REC["STEPS"]].sum())
+    assert np.array_equal(rec, want[rows])

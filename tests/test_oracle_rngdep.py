@@ -39,3 +39,36 @@ def test_fan_records_bitexact(gold, oracle, amp, mode):
     if want_smp:
         assert nsmp == int(gold[f"nsmp_{tag}"])
         assert np.array_equal(smp[gold[f"smp_idx_{tag}"]], gold[f"smp_{tag}"])
+
+
+def test_alt_config_bitexact(gold, oracle):
+    """off-centre elevated source, other frequency and absorption scale, tighter box, two bounces (the ground stays at 0: this set tapers the winds around z_grnd
+    when it LOADS, and `oracle` loaded with 0)"""
+    cfg = H.make_cfg(EQ, bounces=2, calc_amp=True, mode=0, src=(120.0, -60.0, 1.0), freq=0.4, tweak_abs=0.6, xy_limits=(-700.0, 900.0, -600.0, 700.0))
+    steps, rec, _, _ = oracle.fan(cfg, gold["theta"], gold["phi"])
+    assert steps == int(gold["steps_alt"])
+    assert np.array_equal(rec, gold["rec_alt"])
+
+
+# ---- the ragged 7 x 4 jet grid (rngdep_data.write_grid_ragged; make_golden.py ragged3d): loaded with z_grnd = 0.3 as the set's main does ----
+@pytest.fixture(scope="module")
+def oracle_ragged(tmp_path_factory):
+    O = H.Oracle(EQ, met=None)
+    O.load_grid(*RD.write_grid_ragged(str(tmp_path_factory.mktemp("rc")), False, short_paths=False), z_grnd=RD.ragged_load_z_grnd(False))
+    return O
+
+
+def test_ragged_grid_interpolant_bitexact(oracle_ragged):
+    g = RD.ragged_fixture(False)
+    o30, a8 = oracle_ragged.grid_probe(g["probe_x"], g["probe_y"], g["probe_z"])
+    assert np.array_equal(o30, g["probe_out30"]) and np.array_equal(a8, g["probe_api8"])
+
+
+@pytest.mark.parametrize("tag,rows", [("b_amp1", [15, 17, 19]), ("a_amp1", [1]), ("b_amp0", [9]), ("b_f001", [4])])
+def test_ragged_fan_records_bitexact(oracle_ragged, tag, rows):
+    """six rays of the fixture's tables (rays are independent; the fixture script ran the oracle on all of them): a ray launched downwards that arrives three
+    times, the ducted ray that leaves the grid after 27 080 steps, legs that BREAK at the edge after one and two arrivals, 10 Hz and 0.01 Hz"""
+    th, ph, params, want, _, _ = RD.ragged_table(RD.ragged_fixture(False), tag)
+    steps, rec, _, _ = oracle_ragged.fan(H.make_cfg(EQ, **params), th[rows], ph[rows])
+    assert steps == int(want[rows][..., H.REC["STEPS"]].sum())
+    assert np.array_equal(rec, want[rows])
