@@ -187,8 +187,8 @@ struct geoac_ctx {
     bool trace_epochs = false;                    // GEOAC_TRACE_EPOCHS=1: per-epoch live counts on stderr
     bool no_gate = false;                         // GEOAC_NO_GATE=1: post-pass not held back behind the next RK4 launch (A/B measurements)
     bool no_pair = false;                         // GEOAC_NO_PAIR=1: force one lane per ray (A/B measurements)
-    bool range_skip = true;                       // RANGE_SKIP=0: range_skip2 = -1, every row of the spherical stratified set takes the full tests (EqGlobal::checks_fast; tests)
-    bool pole_fast = true;                        // POLE_FAST=0: pole_k = +inf, every step of that set runs with the pole guard (tests)
+    bool range_skip = true;                       // RANGE_SKIP=0: range_skip2 = -1 and a range horizon of one step, every row of the spherical stratified set takes the full tests (EqGlobal::checks_fast, EqGlobal::horizon; tests)
+    bool pole_fast = true;                        // POLE_FAST=0: pole_k = +inf, every step of that set runs with the pole guard and no row has a horizon (tests)
     bool grid_build_host = false;                 // GRID_BUILD=host: evaluation table of the grid sets by the host twin (geoac_grid_table_eq) instead of on the device
     int ev_slack = 72;                            // GEOAC_EV_SLACK: per-epoch event rows of a ray beyond its raypath samples (caustics); tests lower it to reach the overflow path
     int trio = 0;                                 // TRIO=1: slots that would take two lanes per ray run the wave-specialised kernel k_rk4_trio (the ray on one wave, one launch-angle system on each of two more)
@@ -350,6 +350,64 @@ extern "C" void geoac_probe_step_vote_consts(double range_limit, double r_earth,
         if(t_max > 0.0) pole_k = (1.0 + 1e-12) / t_max;
     }
     out[0] = thresh; out[1] = skip2; out[2] = pole_k; out[3] = GEOAC_RCPC_EMAX; out[4] = delta;
+}
+
+// The constants of the step-count horizon (geoac_horizon_steps, geoac_device.h; EqGlobal::horizon in k_rk4's step loop), and what they are derived from.
+// The horizon of a row is a number n of further rows of the same ray on which neither the range test nor the pole_k test can fire; the step
+// loop tests neither before row n + 1 (the step limit is a step count as it stands: k_lim - k).  Both rest on one fact: a step is at most ds_bound = max(min(0.05, ds_max), ds_min) km long (set_ds), and its
+// slopes are components of a unit vector (the group velocity over its modulus), the angular ones over r (and over cos(lat) for the longitude).
+//
+// (Not the vertical limit.  (vert_limit - r) / ds_bound is a bound of the same kind and was built: 948 instructions per step of the two-lane kernel against 950 - and the metric
+// pass SLOWER than the parent, 117.1 against 116.7 ms, the one-lane launches by up to 7 %: under a 140 km top no ray is ever more than 2 800 steps from the limit, so each
+// of the 32 or 64 rays of a wave took its wave out of the loop every 400 - 2 800 steps.  The compare stays in the loop.  profiles/r06_a_vertical_ab.txt)
+//
+// pole.  |dlat| of a row <= delta, the bound on a stage's latitude increment that pole_k is derived with (above: ds_bound over the smallest radius a stage can
+// have, ground radius - 3 ds_bound - any ground radius, not r_earth alone -, times 1 + 1e-12).  The rows that need no guard are those with |tan(lat)| <= 1 / pole_k,
+// |lat'| <= phi_k = atan(1 / pole_k) for the latitude lat' folded into [-pi/2, pi/2] (a ray over a pole has |lat| > pi/2; |sin| and |cos| fold it).  The latitude
+// left is phi_k - |lat'| >= sin(phi_k - |lat'|) = sin(phi_k) |cos(lat)| - cos(phi_k) |sin(lat)| =: g (for 0 <= phi_k - |lat'| <= pi/2; g <= 0: the row is beyond, n = 0), and a move
+// by dlat moves |lat'| by at most |dlat|.  n = (g - 1e-12) / delta: 1e-12 against the rounding of the carried sin / cos (1e-16) and of g.  pole_k = +inf (POLE_FAST=0, or no
+// bound on the step): sin(phi_k) = 0, g <= 0 on every row, n = 0 - every row is tested and every step guarded, as before.
+//
+// range.  The great-circle angle between consecutive rows is at most adv = delta (1 + 1e-4).  The row moves by dlat = ds sum w_i a_i / r_i and dlon = ds sum w_i b_i / (r_i cos(lat_i))
+// with a_i^2 + b_i^2 <= 1 (i: the stages).  The straight line in (lat, lon) between the rows is no shorter than the great circle and has length <= sqrt(dlat^2 + c^2 dlon^2),
+// c the largest |cos(lat)| along it.  Up to its horizon the ray stands on rows that passed the pole_k test (the pole term), and from such a row every latitude within delta
+// has cos(lat) within GEOAC_RCPC_EMAX (1e-5) of the row's - that is what pole_k was derived for -, so c / |cos(lat_i)| <= 1 + 3e-5 and the length is
+// <= (1 + 3e-5) ds sum w_i sqrt(a_i^2 + b_i^2) / r_i <= (1 + 3e-5) delta.  (Beyond the pole_k latitude, where a stage next to the pole can throw the longitude anywhere,
+// no such bound holds - and none is used: there the pole term is 0 and every row takes the range test, as it did before.)  The angle from the source to the row is
+// d = 2 asin(sqrt(hav)), the limit L = 2 asin(sqrt(range_thresh)); sin is 1-Lipschitz, so (L - d) / 2 >= sqrt(range_thresh) - sqrt(hav), and the triangle inequality
+// on the sphere gives d_n <= d + n adv.  n = (S - sqrt(hav)) (2 / adv) with S = sqrt(range_thresh) - 5e-8: the kernel's hav is within 3e-16 of the real one (above),
+// its root within sqrt(3e-16) = 1.8e-8; 5e-8 of half-angle is 0.6 m of range.  No asin: the bound loses the factor cos(L / 2R) at most (0.993 at 1500 km) - from range 0 the
+// first horizon at 1500 km is 29 900 steps of 30 000.  The degenerate limits as range_skip2 has them: a test that can never fire (limit >= pi R) has S = 1e300 and
+// a period of 1; limit <= 0, a NaN, a limit of metres (S <= 0): period 0, n = 0, every row is tested.  ds_min = ds_max = -1 (ds_bound <= 0): both periods 0.
+// out[7]: the six constants in the order of geoac_device.h's HZ_ enumeration, then ds_bound.
+extern "C" void geoac_probe_step_horizon_consts(double range_limit, double r_earth, double ground_radius, double ds_min, double ds_max, double* out){
+    double c[5];
+    geoac_probe_step_vote_consts(range_limit, r_earth, ground_radius, ds_min, ds_max, c);
+    const double thresh = c[0], pole_k = c[2], delta = c[4];
+    const double ds_top = ds_max < GEOAC_DS_TOP ? ds_max : GEOAC_DS_TOP;
+    const double dsb = ds_top > ds_min ? ds_top : ds_min;
+    const bool stepped = dsb > 0.0 && delta > 0.0 && delta < (double)INFINITY;
+    for(int q = 0; q < GEOAC_HZ_N; q++) out[q] = 0.0;
+    if(stepped){
+        const double adv = delta * (1.0 + 1e-4);
+        if(thresh >= 2.0){ out[HZ_RNG_S] = 1e300; out[HZ_RNG_PER] = 1.0; }
+        else if(thresh > 0.0){
+            const double S = sqrt(thresh) - 5e-8;
+            if(S > 0.0){ out[HZ_RNG_S] = S; out[HZ_RNG_PER] = 2.0 / adv; }
+        }
+        if(pole_k < (double)INFINITY && pole_k > 0.0){
+            const double h = sqrt(1.0 + pole_k * pole_k);
+            out[HZ_POLE_S] = 1.0 / h; out[HZ_POLE_C] = pole_k / h;
+            out[HZ_POLE_PER] = 1.0 / delta;
+        } else out[HZ_POLE_C] = 1.0;
+        out[HZ_POLE_EPS] = 1e-12;
+    }
+    out[GEOAC_HZ_N] = dsb;
+}
+
+// geoac_horizon_steps on n rows (hav as EqGlobal::range_far forms it, sin / cos of the latitude) with the constants hz[] of the function above
+extern "C" void geoac_probe_step_horizon(const double* hz, int n, const double* hav, const double* slat, const double* clat, int* out){
+    for(int i = 0; i < n; i++) out[i] = geoac_horizon_steps(hz, hav[i], slat[i], clat[i]);
 }
 
 // ---- launch-plan options (A/B measurements, tests; results never depend on them) ----
@@ -947,7 +1005,13 @@ static int fan_launch_once(geoac_ctx* ctx){
         geoac_probe_step_vote_consts(p.range_limit, p.r_earth, P.ground, p.ds_min, p.ds_max, c);
         P.range_skip2 = ctx->range_skip ? c[1] : -1.0;
         P.pole_k = ctx->pole_fast ? c[2] : (double)INFINITY;
-    }
+        // the step-count horizon of the step loop.  RANGE_SKIP=0: a range period of 0 - no row is ever skipped; POLE_FAST=0: the pole term of pole_k = +inf, 0 on every row
+        double h[GEOAC_HZ_N + 1];
+        geoac_probe_step_horizon_consts(p.range_limit, p.r_earth, P.ground, p.ds_min, p.ds_max, h);
+        if(!ctx->range_skip) h[HZ_RNG_PER] = 0.0;
+        if(!ctx->pole_fast){ h[HZ_POLE_S] = 0.0; h[HZ_POLE_C] = 1.0; h[HZ_POLE_PER] = 0.0; }
+        for(int q = 0; q < GEOAC_HZ_N; q++) P.hz[q] = h[q];
+    } else for(int q = 0; q < GEOAC_HZ_N; q++) P.hz[q] = 0.0;
     P.src[0] = p.src[0]; P.src[1] = p.src[1]; P.src[2] = p.src[2];
     P.freq = p.freq; P.tweak_abs = p.tweak_abs;
     {   // SuthBass reference state: T_o, P_o at abscissa z_grnd (Atmo_State.Absorption.Global.cpp:31-32 passes the km

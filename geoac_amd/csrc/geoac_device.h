@@ -33,6 +33,7 @@
 #define GEOAC_DEVICE_H_
 
 #include <stdint.h>
+#include <math.h>
 
 #define GEOAC_SEGW      14      // doubles per segment in the T/u/v table
 #define GEOAC_MAXE      18
@@ -45,7 +46,30 @@
 #ifndef GEOAC_RCPC_EMAX
 #define GEOAC_RCPC_EMAX 1.0e-5  // largest |1 - cos(lat) / cos(lat of stage 0)| the Newton step of the stage reciprocals is trusted with (global_base; its cube, 1e-15 - up to 9 ulp -, is the error left)
 #endif
-#define GEOAC_CNT_PPFLAG 28     // counters[+0]: entries of the fix-up list of the current k_postpass_tab launch; counters[+1]: path segments of the fan the absorption table did not serve (evaluated exactly by k_ppfix)
+// The step-count horizon of the spherical stratified set's step loop (k_rk4, EqGlobal::horizon): how many further rows of a ray can be neither beyond the range
+// limit nor beyond the pole_k latitude - one function for the kernel and for the host probe (geoac_probe_step_horizon), so that
+// the rule the tests check is the rule the kernel runs.  hz[]: the constants of geoac_probe_step_horizon_consts (geoac_api.cpp: what they bound and why).
+//   range:    the angle left to the limit is at least 2 (sin(limit / 2R) - sqrt(hav)) - sin is 1-Lipschitz -, a row moves by at most 2 / HZ_RNG_PER of angle;
+//   pole:     the latitude left to the pole_k latitude phi_k is at least sin(phi_k - |lat|) = sin(phi_k) |cos(lat)| - cos(phi_k) |sin(lat)| (folded over the poles by the
+//             absolute values), a row moves by at most 1 / HZ_POLE_PER of latitude.
+// Either term below 1, or a NaN anywhere: 0, the next row is tested.  (No a * b + c that one compiler could fuse and another not: the count must not depend on the kernel.)
+enum { HZ_RNG_S = 0, HZ_RNG_PER, HZ_POLE_S, HZ_POLE_C, HZ_POLE_EPS, HZ_POLE_PER, GEOAC_HZ_N };
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline int geoac_horizon_steps(const double* hz, double hav, double slat, double clat){
+#ifdef __clang__
+    #pragma clang fp contract(off)
+#endif
+    const double n_r = (hz[HZ_RNG_S] - sqrt(fabs(hav))) * hz[HZ_RNG_PER];
+    const double ps = hz[HZ_POLE_S] * fabs(clat), pc = hz[HZ_POLE_C] * fabs(slat);
+    const double n_p = ((ps - pc) - hz[HZ_POLE_EPS]) * hz[HZ_POLE_PER];
+    if(!((n_r >= 1.0) && (n_p >= 1.0))) return 0;
+    const double n = n_r < n_p ? n_r : n_p;
+    return n < 2.0e9 ? (int)n : 2000000000;
+}
+
+#define GEOAC_CNT_PPFLAG 28    // counters[+0]: entries of the fix-up list of the current k_postpass_tab launch; counters[+1]: path segments of the fan the absorption table did not serve (evaluated exactly by k_ppfix)
 
 // per-ray state slots (SoA rows of the state buffer)
 enum {
@@ -64,6 +88,7 @@ enum {
     ST_LTT    = 34,     // post-pass per-leg partial sums (arrivals-only form of Q7)
     ST_LAT    = 35,
     ST_YM2    = 36,     // row k-2 of the current leg (Cartesian sets: quadratic ground intercept), up to 18 values (3D.RngDep)
+    ST_KHZ    = 36,     // spherical stratified set (no row k-2 there): the ray's step-count horizon k_hz of the current leg (as double, exact; geoac_horizon_steps)
     ST_DPREV  = 54,     // Jacobian of the previous row (WriteCaustics)
     ST_NSTATE = 55
 };
@@ -100,6 +125,7 @@ struct GeoacDevParams {
     double  range_skip;             // Global: while (|lat - lat_src| + |lon - lon_src|) / 2 stays below this, the range test cannot fire (EqGlobal::checks)
     double  range_skip2;            // Global, step loop: while q = dlat^2 + |cos(lat_src) cos(lat)| dlon^2 stays below this, the range test cannot fire (EqGlobal::checks_fast; -1: never skipped)
     double  pole_k;                 // Global, step loop: a row with |sin(lat)| pole_k <= |cos(lat)| starts a step whose stage reciprocals need no guard (EqGlobal::checks_fast; +inf: every step guarded)
+    double  hz[GEOAC_HZ_N];         // Global, step loop: the constants of the step-count horizon (geoac_horizon_steps; set by geoac_probe_step_horizon_consts)
     double  src[3];                 // as in geoac_params
     double  freq, tweak_abs;
     double  T_o, P_o;               // SuthBass reference temperature / pressure (ground), host-evaluated from the spline

@@ -272,6 +272,7 @@ DEVINL void duo_base(const GeoacDevParams& P, const double* tab13, DuoPort& pt, 
         #pragma unroll
         for(int e = 0; e < 6; e++) st[(ST_Y0 + e) * np] = y[e];
         st[ST_K * np] = (double)k; st[ST_LEG * np] = (double)leg; st[ST_DONE * np] = done ? 1.0 : 0.0;
+        st[ST_KHZ * np] = 0.0;                                   // (this kernel keeps no step-count horizon: a k_rk4 launch that takes the ray over tests its next row)
         st[ST_HMAX * np] = hmax; st[ST_SEG * np] = (double)(seg / 13);
         #pragma unroll
         for(int q = 0; q < 6; q++) st[(ST_AUX0 + q) * np] = C.a[q];

@@ -942,6 +942,26 @@ template <bool AMP_> struct EqGlobal {
     }
     // the pole_k test on the CURRENT row (the carried values after accept / restart / resume): true = the step from here runs guarded
     static DEVINL bool near_pole(const GeoacDevParams& P, const RayCtx& C){ return !(fabs(C.cur[0]) * P.pole_k <= fabs(C.cur[1])); }
+    // The tests of k_rk4's step loop where every rare one is answered by a step count (the instantiations without sample capture): the carried sin / cos of the
+    // latitude, as in checks_fast, the vertical limit and the ground.  Range limit, pole_k latitude and step limit cannot fire before the ray's horizon k_hz
+    // (`horizon` below): the loop compares the row index with it, and the row that reaches it takes those tests outside the loop, as a voted row.
+    static DEVINL void checks_hz(const GeoacDevParams& P, RayCtx& C, const double* yn, bool& brk, bool& gnd){
+        const double dl = yn[1] - C.a[0];
+        rot_small(C.a[1], C.a[2], dl, C.t[0], C.t[1]);
+        if(__builtin_expect(fabs(dl) > GEOAC_ROT_MAX, 0)){ C.a[0] = yn[1]; fsincos(yn[1], C.a[1], C.a[2]); C.t[0] = C.a[1]; C.t[1] = C.a[2]; }   // (rare, per ray: the rotation is discarded)
+        brk = yn[0] > P.vert_limit;
+        gnd = yn[0] < P.ground;
+    }
+    // The step-count horizon of the row y whose sin / cos of latitude are C.cur (a voted row after its tests, or row 0 of a leg): the number of further rows on which
+    // none of the rare tests can fire (geoac_horizon_steps, geoac_device.h; the bounds: geoac_api.cpp).  The haversine is range_far's, from the longitude reference
+    // that range_far or restart has just left within GEOAC_ROT_MAX of the row - the ray's own rows decide the count, not its wave, its chunk or its launch.
+    static DEVINL int horizon(const GeoacDevParams& P, const RayCtx& C, const double* y){
+        double tp0, tp1;
+        rot_small(C.a[4], C.a[5], (y[2] - P.src[2] * kPi / 180.0) - C.a[3], tp0, tp1);
+        const double sl0 = P.src_trig[0], cl0 = P.src_trig[1];
+        const double hav = __builtin_fma(cl0 * C.cur[1], 0.5 * (1.0 - tp1), 0.5 * (1.0 - __builtin_fma(C.cur[1], cl0, C.cur[0] * sl0)));
+        return geoac_horizon_steps(P.hz, hav, C.cur[0], C.cur[1]);
+    }
     static DEVINL void accept(RayCtx& C){ C.cur[0] = C.t[0]; C.cur[1] = C.t[1]; }
     static DEVINL void restart(const GeoacDevParams& P, RayCtx& C, const double* y){      // start of a leg: the reflected row is the new reference
         C.a[0] = y[1]; fsincos(y[1], C.a[1], C.a[2]);
@@ -1815,6 +1835,10 @@ __global__ void __launch_bounds__(256) k_init(GeoacDevParams P){
     for(int e = 0; e < GEOAC_MAXE; e++) st[(ST_Y0 + e) * np] = y[e];
     st[ST_C0 * np] = C.c0; st[ST_NU0 * np] = C.nu0;
     for(int q = 0; q < 6; q++) st[(ST_AUX0 + q) * np] = C.a[q];
+    if constexpr (EQ::SEG1D){ if constexpr (EQ::POLE_FAST){          // the first leg's step-count horizon, from row 0 as at every leg start (k_rk4)
+        const int n = EQ::horizon(P, C, y), left = (int)(P.step_limit - 1) - 1;
+        st[ST_KHZ * np] = (double)(1 + (n < left ? n : (left > 0 ? left : 0)));
+    } }
     st[ST_SEG * np] = P.gtab ? -1.0 : (double)seg_guess(P.seg, P, clampd(y[EQ::HIDX], P.x_min, P.x_max));   // grid sets: search from scratch
     double* R = P.rec + (size_t)ray * (P.bounces + 1) * GEOAC_REC_STRIDE;
     for(int q = 0; q < (P.bounces + 1) * GEOAC_REC_STRIDE; q++) R[q] = 0.0;
@@ -2082,9 +2106,13 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
         //    (row k-1, the three-stage sum, the last slope); the leg end is worked off outside and the wave re-enters.  Inside the loop a row is
         //    never merged with the outcome of a rare path, which is what cost ~45 register moves per step before (a few hundred leg ends per
         //    wave and fan against 50 000 steps).
-        //  * (spherical set) the tests a row rarely needs ride in the same vote: `slow` of EQ::checks_fast - the range test once the ray is within ~0.25 % of the
-        //    limit, a row from which the stage reciprocals need their pole guard.  The voted row runs the range test outside (EQ::range_far, the slow lanes
-        //    only: what a row's tests are depends on the ray's own rows, not on its wave's), and while a lane of the wave
+        //  * (spherical set) the tests a row rarely needs ride in the same vote, as ONE integer compare: the row index against the ray's horizon k_hz, before
+        //    which neither the range limit, nor a row from which the stage reciprocals need their pole guard, nor the step limit
+        //    can be reached (EQ::horizon: a step is at most ds_bound long).  The row that reaches it takes those tests outside (the lanes whose own horizon
+        //    expired only: what a row's tests are depends on the ray's own rows, not on its wave's, its chunk or its launch - k_hz is part of the ray's state)
+        //    and gets a new horizon from its exact values; every leg starts with one.  The chunk-room bound is a step count too and shares the compare
+        //    (k_stop), but is per launch and never stored.  (The sample-capturing instantiations keep `slow` of EQ::checks_fast: the range test once the ray
+        //    is within ~0.25 % of the limit.)  While a lane of the wave
         //    stands on a row that failed the pole_k test the wave takes GUARDED steps one at a time - the same step with global_base's guard, straight into the
         //    voted-row path - before it re-enters the fast loop, whose global_base has no guard.  Same bits on either path: DESIGN 3.
         //    (The sample-capturing instantiations keep the guard in their loop and have no second step: with open_step's capture code twice they spill to scratch.
@@ -2143,6 +2171,7 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
         }
         } else {
         constexpr bool PF = !SMP;                                     // the fast loop runs without the pole guard, and a guarded step exists
+        int k_hz = PF ? (int)st[ST_KHZ * np] : 0;                     // the ray's horizon: part of its state (k_init: from row 0 of the ray)
         while(__any((nr + 2 <= P.s_rows) && !done)){                  // (wave-uniform)
             bool ev = false, pend = false, slow = false;
             double dy[E], ys[E], w6 = 0.0;                            // at a vote: the last slope, the sum of the first three stages, ds / 6
@@ -2172,25 +2201,37 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
                 double t[EQ::NB];
                 #pragma unroll
                 for(int e = 0; e < EQ::NB; e++) t[e] = __builtin_fma(dy[e], ds_6, ys[e]);
-                EQ::template checks_fast<PF>(P, C, y, t, k + 1, brk, gnd, slow);
-                lim = (k + 1 >= k_lim);                               // Solver.cpp loop bound; never reached on sane inputs
-                ev = brk || gnd || lim;
+                if constexpr (PF){ EQ::checks_hz(P, C, t, brk, gnd); ev = brk || gnd; }             // (range, pole_k latitude and step limit: not before row k_hz)
+                else {
+                    EQ::template checks_fast<PF>(P, C, y, t, k + 1, brk, gnd, slow);
+                    lim = (k + 1 >= k_lim);                           // Solver.cpp loop bound; never reached on sane inputs
+                    ev = brk || gnd || lim;
+                }
                 return ds_6;
             };
             const bool act = (nr + 2 <= P.s_rows) && !done;
+            // the row index at which this lane leaves the loop whatever the row holds: its horizon, or the row after which its chunk has no room for another step
+            // (nr and k advance together in the loop, so `nr + 3 > s_rows` is a bound on k as well: per launch, and kept apart from the ray's own k_hz)
+            const int k_in = k, room = P.s_rows - 1 - nr;
+            const int k_stop = (k_hz - k < room) ? k_hz : k + room;
             bool guarded = false;
             if constexpr (PF) guarded = __any(act && EQ::near_pole(P, C));
             if(!guarded){
                 if(act) for(;;){                                      // (every lane that enters leaves at the same vote: no exec-mask bookkeeping inside)
                     const double ds_6 = step_parts(BoolC<!PF>());
-                    const bool full = !(nr + 3 <= P.s_rows);            // this lane's chunk has no room for another step after this one
-                    if(__builtin_expect(__any(ev || full || slow), 0)){ pend = true; w6 = ds_6; break; }
+                    bool stop;
+                    if constexpr (PF) stop = ev || (k + 1 >= k_stop);
+                    else {
+                        const bool full = !(nr + 3 <= P.s_rows);        // this lane's chunk has no room for another step after this one
+                        stop = ev || full || slow;
+                    }
+                    if(__builtin_expect(__any(stop), 0)){ pend = true; w6 = ds_6; break; }
                     #pragma unroll
                     for(int e = 0; e < E; e++){
                         if(YM2_REG) ym2[e] = y[e];
                         y[e] = __builtin_fma(dy[e], ds_6, ys[e]);
                     }
-                    k++; steps_here++;
+                    k++; if constexpr (!PF) steps_here++;              // (PF: counted at the vote, from the difference of k)
                     put_row(y);
                     EQ::accept(C);
                 }
@@ -2198,11 +2239,25 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
             if(pend){                                                 // (rare) the row that was voted on
                 #pragma unroll
                 for(int e = 0; e < E; e++) ys[e] = __builtin_fma(dy[e], w6, ys[e]);
+                bool renew = false;
+                if constexpr (PF){
+                    // a lane whose OWN horizon has expired takes the rare tests on this row, exactly as a row of `checks` would: the range test (the row's position is
+                    // in ys now, its sin / cos of latitude in C.t) beside the vertical limit it has taken, and the loop bound.  For every other lane they cannot fire.
+                    renew = (k + 1 >= k_hz);
+                    lim = false;
+                    if(renew){
+                        brk = EQ::range_far(P, C, ys[2] - P.src[2] * kPi / 180.0) || brk;
+                        lim = (k + 1 >= k_lim);                       // Solver.cpp loop bound; never reached on sane inputs
+                    }
+                    ev = brk || gnd || lim;
+                    k++; steps_here += (unsigned long long)(k - k_in);
+                } else {
                 if(slow){                                             // the range test on the same row (its position is in ys now, the bits the fast tests saw; its sin / cos of latitude in C.t)
                     brk = EQ::range_far(P, C, ys[2] - P.src[2] * kPi / 180.0) || brk;
                     ev = brk || gnd || lim;
                 }
                 k++; steps_here++;
+                }
                 put_row(ys);
                 EQ::accept(C);                                        // (a leg end sets the carried values anew: restart)
                 if(ev) leg_end(y, ys, ym2);
@@ -2210,8 +2265,17 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
                     #pragma unroll
                     for(int e = 0; e < E; e++){ if(YM2_REG) ym2[e] = y[e]; y[e] = ys[e]; }
                 }
+                if constexpr (PF){
+                    // the new horizon, from the exact values of the row the lane now stands on: the tested row, or row 0 of a new leg (every leg starts with one).
+                    // Rows k + 1 .. k + n cannot fire, row k + n + 1 is the next one tested - and no row beyond the step limit's goes untested
+                    if((renew && !ev) || (ev && !done)){
+                        const int n = EQ::horizon(P, C, y), left = k_lim - k - 1;
+                        k_hz = k + 1 + (n < left ? n : (left > 0 ? left : 0));
+                    }
+                }
             }
         }
+        if constexpr (PF) st[ST_KHZ * np] = (double)k_hz;              // (the horizon goes with the ray into the next launch, whichever kernel and chunk that is)
         }
     } else {
     // COOP: wave-uniform loop (every lane stays while any lane of the wave has work; `act` predicates this lane's own work).

@@ -47,6 +47,16 @@ int geoac_probe_grid(geoac_ctx* ctx, int n, const double* a0, const double* a1, 
  * the guard's threshold; delta, the bound on a stage's latitude increment that pole_k is derived with.  ground_radius = r_earth + z_grnd. */
 void geoac_probe_step_vote_consts(double range_limit, double r_earth, double ground_radius, double ds_min, double ds_max, double* out);
 
+/* spherical stratified set: the step-count horizon of the step loop - the number of further rows of a ray on which neither the range test nor the test for the
+ * pole_k latitude can fire, so that the loop tests neither before (host arithmetic, as above; the derivation stands with the function).  out[7]: S = sin(range_limit / 2 r_earth) less its margin and the range period - n_range = (S - sqrt(hav)) period; sin and cos of the
+ * pole_k latitude, the margin and the pole period - n_pole = (sin_k |cos(lat)| - cos_k |sin(lat)| - margin) period; the horizon is the floor of the smaller,
+ * 0 if one of them is below 1 or a NaN; then ds_bound, the longest step [km]. */
+void geoac_probe_step_horizon_consts(double range_limit, double r_earth, double ground_radius, double ds_min, double ds_max, double* out);
+
+/* the horizon rule itself, the function the kernel calls, on n rows: hav as the range test forms it (EqGlobal::range_far), sin / cos of the latitude;
+ * hz = the first six constants of the function above */
+void geoac_probe_step_horizon(const double* hz, int n, const double* hav, const double* slat, const double* clat, int* out);
+
 #ifdef __cplusplus
 }
 #endif
