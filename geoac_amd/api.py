@@ -382,6 +382,23 @@ class FanContext:
         x, y, z, T, u, v, rho = (_arr(a) for a in (x, y, z, T, u, v, rho))
         self._chk(self.lib.geoac_upload_atmo_3d(self._h, len(x), len(y), len(z), _p(x), _p(y), _p(z), _p(T), _p(u), _p(v), _p(rho)))
         self._grid_dims = (len(x), len(y), len(z))
+        self.n_members = 1
+
+    def upload_atmo_3d_ensemble(self, x, y, z, T, u, v, rho):
+        """K grids of profiles on the shared nodes x, y, z (geoac_upload_atmo_3d_ensemble): T, u, v, rho [K][nx][ny][nz], each member as upload_atmo_3d
+        takes it.  fetch() / run() then return records of shape (K, n_rays, legs, 32)."""
+        x, y, z = (_arr(a) for a in (x, y, z))
+        T, u, v, rho = (_arr(a) for a in (T, u, v, rho))
+        if T.ndim == 3:
+            T, u, v, rho = (a[None] if a.ndim == 3 else a for a in (T, u, v, rho))
+        if T.ndim != 4 or x.ndim != 1 or y.ndim != 1 or z.ndim != 1 or T.shape[1:] != (len(x), len(y), len(z)) or any(a.shape != T.shape for a in (u, v, rho)):
+            raise GeoAcError(f"upload_atmo_3d_ensemble: T, u, v, rho must be [K][nx][ny][nz] arrays with nx, ny, nz = len(x), len(y), len(z) "
+                             f"(got x {x.shape}, y {y.shape}, z {z.shape}, T {T.shape}, u {u.shape}, v {v.shape}, rho {rho.shape})")
+        T, u, v, rho = (_arr(a) for a in (T, u, v, rho))
+        K = T.shape[0]
+        self._chk(self.lib.geoac_upload_atmo_3d_ensemble(self._h, K, len(x), len(y), len(z), _p(x), _p(y), _p(z), _p(T), _p(u), _p(v), _p(rho)))
+        self._grid_dims = (len(x), len(y), len(z))
+        self.n_members = K
 
     def grid_table(self):
         """the evaluation table the last upload_atmo_3d built on the device (layout of geoac_grid_table_eq)"""
@@ -393,6 +410,24 @@ class FanContext:
 
     def load_grid(self, prefix, locx, locy, fmt="zTuvdp", z_grnd=0.0):
         """Spline_Multi_G2S equivalent: <prefix><n>.met files + loc_x / loc_y node files"""
+        g = self._read_grid(prefix, locx, locy, fmt, z_grnd)
+        self.upload_atmo_3d(g["x"], g["y"], g["z"], g["T"], g["u"], g["v"], g["rho"])
+        return g
+
+    def load_grid_ensemble(self, grids, fmt="zTuvdp", z_grnd=0.0):
+        """one grid specification (prefix, locx, locy) per member, each read as load_grid reads it; the members must share their x, y and z nodes"""
+        grids = [tuple(g) for g in grids]
+        if not grids:
+            raise GeoAcError("load_grid_ensemble: no grids")
+        mem = [self._read_grid(*g, fmt, z_grnd) for g in grids]
+        for g, a in zip(grids[1:], mem[1:]):
+            for k in ("x", "y", "z"):
+                if a[k].shape != mem[0][k].shape or not np.array_equal(a[k], mem[0][k]):
+                    raise GeoAcError(f"load_grid_ensemble: {g} has other {k} nodes than {grids[0]} (an ensemble's members share their nodes)")
+        self.upload_atmo_3d_ensemble(mem[0]["x"], mem[0]["y"], mem[0]["z"], *[np.stack([a[k] for a in mem]) for k in ("T", "u", "v", "rho")])
+        return mem
+
+    def _read_grid(self, prefix, locx, locy, fmt, z_grnd):
         nx, ny, nz = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         if self.lib.geoac_grid_dims(prefix.encode(), locx.encode(), locy.encode(), ctypes.byref(nx), ctypes.byref(ny), ctypes.byref(nz)):
             raise GeoAcError(f"cannot read grid {prefix}")
@@ -403,7 +438,6 @@ class FanContext:
                                       nx, ny, nz, _p(x), _p(y), _p(z), *[_p(f) for f in F])
         if rc:
             raise GeoAcError(f"geoac_grid_load_eq -> {rc}")
-        self.upload_atmo_3d(x, y, z, *F)
         return dict(x=x, y=y, z=z, T=F[0], u=F[1], v=F[2], rho=F[3])
 
     def load_met(self, path, fmt="zTuvdp"):

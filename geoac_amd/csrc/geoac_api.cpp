@@ -156,6 +156,7 @@ struct geoac_ctx {
     std::vector<double> gx, gy;
     DevBuf d_gx, d_gy, d_gz, d_gtab, d_gtab8, d_consts;      // d_gtab8: packed records the Cartesian kernels read (geoac_rngdep.h); d_gtab: the full table
     size_t gtab_bytes = 0;           // of the table the kernels read
+    size_t gtab_stride = 0;          // grid ensembles (geoac_upload_atmo_3d_ensemble): doubles from one member's table to the next in the buffer the kernels read; 0: a single grid
     bool have_grid = false;
     // device
     DevBuf seg, rhot, theta, phi, state, rec, counters;
@@ -566,10 +567,15 @@ int geoac_destroy(geoac_ctx* ctx){
 // parameters and launch-plan options: for callers that run several independent fans at once (the eigenray searches integrate the ray groups
 // of a decision round concurrently, each group on its own context and streams).  Valid until the source uploads another atmosphere or is
 // destroyed; destroy the clone first.
+// the way out of an ensemble, for the messages of the calls that refuse one
+static const char* ens_hint(const geoac_ctx* ctx){
+    return ctx->have_grid ? "(geoac_upload_atmo_3d_ensemble); upload a single grid first" : "(geoac_upload_atmo_1d_ensemble); upload a single profile first";
+}
+
 int geoac_clone(geoac_ctx* src, geoac_ctx** out){
     if(!src || !out) return GEOAC_E_INVALID;
     if(!src->have_atmo) return fail(src, GEOAC_E_INVALID, "clone: no atmosphere uploaded");
-    if(src->n_members > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
+    if(src->n_members > 1) return fail(src, GEOAC_E_UNSUPPORTED, std::string("clone: not available for an ensemble ") + ens_hint(src));
     if(src->n_src > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a source set is active (geoac_set_sources); set a single source first");
     if(src->n_freq > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a frequency set is active (geoac_set_frequencies); set a single frequency first");
     geoac_ctx* c = nullptr;
@@ -673,7 +679,7 @@ int geoac_refuse_ensemble(geoac_ctx* ctx, const char* what){
     if(ctx->n_src > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a source set is active (geoac_set_sources); set a single source first");
     if(ctx->n_freq > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a frequency set is active (geoac_set_frequencies); set a single frequency first");
     if(ctx->n_members <= 1) return GEOAC_OK;
-    return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
+    return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available for an ensemble " + ens_hint(ctx));
 }
 
 int geoac_get_members(geoac_ctx* ctx, int* n_members){
@@ -686,7 +692,8 @@ int geoac_set_sources(geoac_ctx* ctx, int n_src, const double* src){
     if(!ctx) return GEOAC_E_INVALID;
     if(n_src < 1 || !src) return fail(ctx, GEOAC_E_INVALID, "set_sources: n_src must be at least 1 and src not NULL");
     if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
-        return fail(ctx, GEOAC_E_UNSUPPORTED, "set_sources: source sets are available for the stratified equation sets only");
+        return fail(ctx, GEOAC_E_UNSUPPORTED, (n_src > 1 && ctx->n_members > 1) ? "set_sources: not available for a grid ensemble (geoac_upload_atmo_3d_ensemble): source sets are available for the stratified equation sets only"
+                                                                                 : "set_sources: source sets are available for the stratified equation sets only");
     if((long long)n_src * ctx->n_members > GEOAC_MAX_MEMBERS)
         return fail(ctx, GEOAC_E_INVALID, "set_sources: " + std::to_string(n_src) + " sources x " + std::to_string(ctx->n_members) + " profiles exceed the " +
                     std::to_string(GEOAC_MAX_MEMBERS) + " members of a launch");
@@ -711,7 +718,8 @@ int geoac_set_frequencies(geoac_ctx* ctx, int n_freq, const double* freq_hz){
     for(int f = 0; f < n_freq; f++)
         if(!std::isfinite(freq_hz[f]) || !(freq_hz[f] > 0.0)) return fail(ctx, GEOAC_E_INVALID, "set_frequencies: every frequency must be finite and greater than 0");
     if(ctx->eqset != GEOAC_EQ_2D && ctx->eqset != GEOAC_EQ_3D && ctx->eqset != GEOAC_EQ_GLOBAL)
-        return fail(ctx, GEOAC_E_UNSUPPORTED, "set_frequencies: frequency sets are available for the stratified equation sets only");
+        return fail(ctx, GEOAC_E_UNSUPPORTED, (n_freq > 1 && ctx->n_members > 1) ? "set_frequencies: not available for a grid ensemble (geoac_upload_atmo_3d_ensemble): frequency sets are available for the stratified equation sets only"
+                                                                                  : "set_frequencies: frequency sets are available for the stratified equation sets only");
     if(n_freq > 1 && ctx->n_members > 1)
         return fail(ctx, GEOAC_E_UNSUPPORTED, "set_frequencies: not available for an ensemble (geoac_upload_atmo_1d_ensemble); upload a single profile first");
     if(n_freq > 1 && ctx->n_src > 1)
@@ -736,55 +744,80 @@ int geoac_get_frequencies(geoac_ctx* ctx, int* n_freq){
     return GEOAC_OK;
 }
 
-int geoac_upload_atmo_3d(geoac_ctx* ctx, int nx, int ny, int nz, const double* x, const double* y, const double* z,
-                         const double* T, const double* u, const double* v, const double* rho){
-    if(!ctx || nx < 2 || ny < 2 || nz < 3 || !x || !y || !z || !T || !u || !v || !rho) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: bad arguments");
-    if(ctx->eqset != GEOAC_EQ_3D_RNGDEP && ctx->eqset != GEOAC_EQ_GLOBAL_RNGDEP) return fail(ctx, GEOAC_E_UNSUPPORTED, "grid atmosphere needs one of the range-dependent equation sets");
-    for(int i = 1; i < nx; i++) if(!(x[i] > x[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: x not strictly increasing");
-    for(int i = 1; i < ny; i++) if(!(y[i] > y[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: y not strictly increasing");
-    for(int i = 1; i < nz; i++) if(!(z[i] > z[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: z not strictly increasing");
+// K grids of profiles on the nodes x, y, z (K = 1: geoac_upload_atmo_3d); fields [K][nx][ny][nz].  The K evaluation tables lie back to back at a fixed member
+// stride (a multiple of 256 bytes: the records' line alignment holds in every member), each built by the builder of a single grid from that member's fields
+// alone, in member order: table m is bit for bit the table a plain upload of grid m builds.
+static int upload_grids(geoac_ctx* ctx, const char* what, int K, int nx, int ny, int nz, const double* x, const double* y, const double* z,
+                        const double* T, const double* u, const double* v, const double* rho){
     HIPCHK(hipSetDevice(ctx->device));
     const size_t tab_n = geoac_grid_table_size(nx, ny, nz), nn = (size_t)nx * ny;
+    const bool packed = ctx->eqset == GEOAC_EQ_3D_RNGDEP && geoac_kernels_cart_rec() == 32;
+    const size_t pack_n = packed ? geoac_gridpack_doubles(nx, ny, nz) : 0;
+    const size_t st_full = K > 1 ? (tab_n + 31) / 32 * 32 : tab_n, st_pack = K > 1 ? (pack_n + 31) / 32 * 32 : pack_n;      // doubles from one member's table to the next
+    if(K > 1){
+        // the members' tables and the builder's scratch against what the device has left (beside what this context's tables hold already)
+        size_t free_b = 0, total_b = 0;
+        if(hipMemGetInfo(&free_b, &total_b) == hipSuccess){
+            const size_t held = (ctx->d_gtab.owned ? ctx->d_gtab.bytes : 0) + (ctx->d_gtab8.owned ? ctx->d_gtab8.bytes : 0);
+            const double need = (double)K * (double)(st_full + st_pack) * sizeof(double) + (double)(4 * nn * nz + geoac_gridbuild_work_doubles(nx, ny, nz)) * sizeof(double);
+            if(need > (double)free_b + (double)held)
+                return fail(ctx, GEOAC_E_NOMEM, std::string(what) + ": " + std::to_string(K) + " members x " + std::to_string(((st_full + st_pack) * sizeof(double)) >> 20) +
+                            " MiB of tables do not fit in the " + std::to_string((free_b + held) >> 20) + " MiB of device memory that are free");
+        }
+    }
     HIPCHK(ctx->d_gx.ensure(sizeof(double) * nx)); HIPCHK(ctx->d_gy.ensure(sizeof(double) * ny)); HIPCHK(ctx->d_gz.ensure(sizeof(double) * nz));
-    HIPCHK(ctx->d_gtab.ensure(sizeof(double) * tab_n));
-    HIPCHK(ctx->d_consts.ensure(sizeof(double) * 8));
+    {   hipError_t e = ctx->d_gtab.ensure(sizeof(double) * st_full * K);
+        if(e == hipErrorOutOfMemory){ (void)hipGetLastError(); return fail(ctx, GEOAC_E_NOMEM, std::string(what) + ": " + std::to_string(K) + " x " + std::to_string((st_full * sizeof(double)) >> 20) + " MiB of tables: out of device memory"); }
+        HIPCHK(e); }
+    HIPCHK(ctx->d_consts.ensure(sizeof(double) * (8 + 3 * (size_t)K)));      // [K][3]: Eq3DRngDep::fan_init writes each member's reference state
     HIPCHK(hipMemcpyAsync(ctx->d_gx.p, x, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_gy.p, y, sizeof(double) * ny, hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(ctx->d_gz.p, z, sizeof(double) * nz, hipMemcpyHostToDevice, ctx->stream));
+    const size_t fld = nn * nz;                                   // doubles per field and member
     if(ctx->grid_build_host){
         // the host builder (geoac_host.cpp), kept as the checker of the device builder and for A/B timing
         std::vector<double> tab(tab_n);
-        geoac_grid_table_eq(ctx->eqset, nx, ny, nz, x, y, z, T, u, v, rho, tab.data());
-        HIPCHK(hipMemcpyAsync(ctx->d_gtab.p, tab.data(), sizeof(double) * tab_n, hipMemcpyHostToDevice, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
+        for(int m = 0; m < K; m++){
+            geoac_grid_table_eq(ctx->eqset, nx, ny, nz, x, y, z, T + m * fld, u + m * fld, v + m * fld, rho + m * fld, tab.data());
+            HIPCHK(hipMemcpyAsync((double*)ctx->d_gtab.p + m * st_full, tab.data(), sizeof(double) * tab_n, hipMemcpyHostToDevice, ctx->stream));
+            HIPCHK(hipStreamSynchronize(ctx->stream));
+        }
     } else {
         // device table (geoac_rngdep.h) built on the device (geoac_gridbuild.hip): 12 vertical spline systems per node + expansion;
         // only the raw fields cross PCIe (32 B per grid point instead of 1 120 B of table per point)
         DevBuf fields, work;
-        HIPCHK(fields.ensure(sizeof(double) * 4 * nn * nz));
+        HIPCHK(fields.ensure(sizeof(double) * 4 * fld));
         hipError_t we = work.ensure(sizeof(double) * geoac_gridbuild_work_doubles(nx, ny, nz));
         if(we != hipSuccess){ fields.release(); return hipfail(ctx, we, "grid table scratch"); }
-        const double* F[4] = { T, u, v, rho };
         hipError_t e = hipSuccess;
-        for(int f = 0; f < 4 && e == hipSuccess; f++)
-            e = hipMemcpyAsync((double*)fields.p + (size_t)f * nn * nz, F[f], sizeof(double) * nn * nz, hipMemcpyHostToDevice, ctx->stream);
-        if(e == hipSuccess) e = geoac_gridbuild_launch(ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP ? 1 : 0, nx, ny, nz, (const double*)ctx->d_gx.p, (const double*)ctx->d_gy.p,
-                                                       (const double*)ctx->d_gz.p, (const double*)fields.p, (double*)work.p, (double*)ctx->d_gtab.p, ctx->stream);
-        if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        for(int m = 0; m < K && e == hipSuccess; m++){
+            const double* F[4] = { T + m * fld, u + m * fld, v + m * fld, rho + m * fld };
+            for(int f = 0; f < 4 && e == hipSuccess; f++)
+                e = hipMemcpyAsync((double*)fields.p + (size_t)f * fld, F[f], sizeof(double) * fld, hipMemcpyHostToDevice, ctx->stream);
+            if(e == hipSuccess) e = geoac_gridbuild_launch(ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP ? 1 : 0, nx, ny, nz, (const double*)ctx->d_gx.p, (const double*)ctx->d_gy.p,
+                                                           (const double*)ctx->d_gz.p, (const double*)fields.p, (double*)work.p, (double*)ctx->d_gtab.p + m * st_full, ctx->stream);
+            if(e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (fields and work are the next member's too)
+        }
         fields.release(); work.release();
         if(e != hipSuccess) return hipfail(ctx, e, "grid table build");
     }
-    ctx->gtab_bytes = sizeof(double) * tab_n;
-    if(ctx->eqset == GEOAC_EQ_3D_RNGDEP && geoac_kernels_cart_rec() == 32){
+    ctx->gtab_bytes = sizeof(double) * tab_n;                     // of ONE member's table: the cooperative gather's 32-bit offsets are relative to the member's base
+    ctx->gtab_stride = K > 1 ? st_full : 0;
+    if(packed){
         // Cartesian kernels read 256-byte line-aligned records (eight cubics: V_x = D_x F, V_y = D_y F are not stored twice)
-        ctx->gtab_bytes = sizeof(double) * geoac_gridpack_doubles(nx, ny, nz);
-        HIPCHK(ctx->d_gtab8.ensure(ctx->gtab_bytes));
-        HIPCHK(geoac_gridpack_launch(nx, ny, nz, (const double*)ctx->d_gtab.p, (double*)ctx->d_gtab8.p, ctx->stream));
+        ctx->gtab_bytes = sizeof(double) * pack_n;
+        ctx->gtab_stride = K > 1 ? st_pack : 0;
+        {   hipError_t e = ctx->d_gtab8.ensure(sizeof(double) * st_pack * K);
+            if(e == hipErrorOutOfMemory){ (void)hipGetLastError(); return fail(ctx, GEOAC_E_NOMEM, std::string(what) + ": " + std::to_string(K) + " x " + std::to_string((st_pack * sizeof(double)) >> 20) + " MiB of packed tables: out of device memory"); }
+            HIPCHK(e); }
+        for(int m = 0; m < K; m++)
+            HIPCHK(geoac_gridpack_launch(nx, ny, nz, (const double*)ctx->d_gtab.p + m * st_full, (double*)ctx->d_gtab8.p + m * st_pack, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
     } else ctx->d_gtab8.release();
     ctx->gnx = nx; ctx->gny = ny; ctx->n_nodes = nz;
     ctx->gx.assign(x, x + nx); ctx->gy.assign(y, y + ny); ctx->x.assign(z, z + nz);
-    ctx->n_members = 1;
+    const int K_was = ctx->n_members;
+    ctx->n_members = K;
     // GeoAc_SetPropRegion (G2S_MultiDimSpline3D.cpp:25-33)
     if(!(ctx->prm.vert_limit == ctx->prm.vert_limit)) ctx->prm.vert_limit = z[nz - 1];
     const double ext[4] = { x[0], x[nx - 1], y[0], y[ny - 1] };
@@ -793,7 +826,33 @@ int geoac_upload_atmo_3d(geoac_ctx* ctx, int nx, int ny, int nz, const double* x
     ctx->atmo_version++; ctx->atmo_gen->fetch_add(1);
     ctx->map_gen++;
     ctx->ran = false;                             // (the probes launch with the tables of the last fan: not after a new upload)
+    if(K != K_was && ctx->have_angles) return layout_angles(ctx);       // (the slot layout depends on K)
     return GEOAC_OK;
+}
+
+int geoac_upload_atmo_3d(geoac_ctx* ctx, int nx, int ny, int nz, const double* x, const double* y, const double* z,
+                         const double* T, const double* u, const double* v, const double* rho){
+    if(!ctx || nx < 2 || ny < 2 || nz < 3 || !x || !y || !z || !T || !u || !v || !rho) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: bad arguments");
+    if(ctx->eqset != GEOAC_EQ_3D_RNGDEP && ctx->eqset != GEOAC_EQ_GLOBAL_RNGDEP) return fail(ctx, GEOAC_E_UNSUPPORTED, "grid atmosphere needs one of the range-dependent equation sets");
+    for(int i = 1; i < nx; i++) if(!(x[i] > x[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: x not strictly increasing");
+    for(int i = 1; i < ny; i++) if(!(y[i] > y[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: y not strictly increasing");
+    for(int i = 1; i < nz; i++) if(!(z[i] > z[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d: z not strictly increasing");
+    return upload_grids(ctx, "upload_atmo_3d", 1, nx, ny, nz, x, y, z, T, u, v, rho);
+}
+
+int geoac_upload_atmo_3d_ensemble(geoac_ctx* ctx, int n_members, int nx, int ny, int nz, const double* x, const double* y, const double* z,
+                                  const double* T, const double* u, const double* v, const double* rho){
+    if(!ctx) return GEOAC_E_INVALID;
+    if(n_members < 1 || n_members > GEOAC_MAX_MEMBERS)
+        return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d_ensemble: n_members must be in 1 .. " + std::to_string(GEOAC_MAX_MEMBERS));
+    if(nx < 2 || ny < 2 || nz < 3) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d_ensemble: at least 2 x 2 profiles of 3 nodes");
+    if(!x || !y || !z || !T || !u || !v || !rho) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d_ensemble: NULL array");
+    if(ctx->eqset != GEOAC_EQ_3D_RNGDEP && ctx->eqset != GEOAC_EQ_GLOBAL_RNGDEP)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "upload_atmo_3d_ensemble: grid ensembles need one of the range-dependent equation sets (stratified sets: geoac_upload_atmo_1d_ensemble)");
+    for(int i = 1; i < nx; i++) if(!(x[i] > x[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d_ensemble: x not strictly increasing");
+    for(int i = 1; i < ny; i++) if(!(y[i] > y[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d_ensemble: y not strictly increasing");
+    for(int i = 1; i < nz; i++) if(!(z[i] > z[i - 1])) return fail(ctx, GEOAC_E_INVALID, "upload_atmo_3d_ensemble: z not strictly increasing");
+    return upload_grids(ctx, "upload_atmo_3d_ensemble", n_members, nx, ny, nz, x, y, z, T, u, v, rho);
 }
 
 int geoac_grid_table_fetch(geoac_ctx* ctx, double* tab, size_t cap){
@@ -1090,6 +1149,7 @@ static int fan_launch_once(geoac_ctx* ctx){
         P.g_lo[0] = ctx->gx.front(); P.g_hi[0] = ctx->gx.back(); P.g_lo[1] = ctx->gy.front(); P.g_hi[1] = ctx->gy.back();
         P.gx = (const double*)ctx->d_gx.p; P.gy = (const double*)ctx->d_gy.p; P.gz = (const double*)ctx->d_gz.p;
         P.gtab = (const double*)(ctx->d_gtab8.p ? ctx->d_gtab8.p : ctx->d_gtab.p); P.dev_consts = (double*)ctx->d_consts.p;
+        P.gtab_stride = ens ? (long long)ctx->gtab_stride : 0;    // (grid ensembles: the member view rebases gtab and dev_consts; no member constants from the host)
         for(int q = 0; q < 4; q++) P.xy_lim[q] = p.xy_limits[q];
     }
     ctx->legs = p.bounces + 1;
@@ -1208,6 +1268,9 @@ static int fan_launch_once(geoac_ctx* ctx){
     const bool scan16_ok = is_grid && ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP && !p.calc_amp && !sampling && ctx->quad_cache && (long long)P.n_pad * 16 / 64 <= 512;
     if(P.lanes_per_ray == 16 && !p.calc_amp && !scan16_ok) P.lanes_per_ray = 4;
     if(P.lanes_per_ray == 4 && !ctx->grid_lanes && !ctx->no_quad && ctx->hex && scan16_ok) P.lanes_per_ray = 16;
+    // grid ensembles: one lane per ray.  The multi-lane and record-cache kernels fill a chip that a small fan leaves idle - K members fill it with rays instead;
+    // GRID_LANES is ignored, lane thinning (SPREAD) is off: a workgroup's 64 lanes are 64 columns of one member (k_rk4, member view)
+    if(is_grid && ens) P.lanes_per_ray = 1;
     // RK4 workgroup shape: with the table in LDS one workgroup owns a CU, so spread the waves over the 256 CUs
     int waves = P.n_pad * P.lanes_per_ray / 64;
     int wpb = (waves + 255) / 256;
@@ -1219,7 +1282,7 @@ static int fan_launch_once(geoac_ctx* ctx){
     // the chip has SIMDs, thin the waves out (1 wave per SIMD is what the kernel's register budget allows)
     P.spread = 1;
     const bool coop_able = is_grid && ctx->grid_coop && ctx->gtab_bytes < (4ull << 30);
-    if(is_grid && P.lanes_per_ray == 1){
+    if(is_grid && P.lanes_per_ray == 1 && !ens){
         // measured (tools/perf_rngdep.py, GEOAC_SPREAD sweep): 2-4 way thinning gains 5-20 %, 8+ loses again (path stores and the
         // post-pass reads scatter), more waves than SIMDs loses a lot.  Only for the per-lane-gather kernel (GRID_COOP=0): a fan that
         // comes here on the default plan has more than 16 384 rays and takes the cooperative kernel unthinned (24 000-ray fan on the
@@ -1724,6 +1787,8 @@ int geoac_launch_view(geoac_ctx* ctx, int slot, GeoacLaunchView* v){
 int geoac_rfn_view(geoac_ctx* ctx, GeoacRfnView* v){
     int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
     if(rc) return rc;
+    if(ctx->have_grid && ctx->n_members > 1)                      // (the Newton rays start from a per-member medium at the source, which this view does not carry for grids)
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_refine: not available for a grid ensemble (geoac_upload_atmo_3d_ensemble); refine the member on a context of its own");
     const int K = ctx->n_members, M = ctx->n_src * K;
     const bool sph = (ctx->eqset == GEOAC_EQ_GLOBAL || ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP);
     ctx->rfn_mem.assign((size_t)M * GEOAC_RFN_MEMW, 0.0);

@@ -18,6 +18,11 @@
 // member-major (member m owns [m S, (m+1) S), S = mem_slots, a multiple of 256 with at least one ray-less slot), the records [K][n_rays][legs][32].
 // A kernel instantiated for ensembles finds its member once per workgroup or wave and works on the member view (member_view) of the block.
 //
+// Grid ensembles (geoac_upload_atmo_3d_ensemble: K grids of profiles on shared x, y, z nodes): gtab holds K evaluation tables back to back at a fixed
+// member stride (gtab_stride doubles; each the table a plain upload of that grid builds, so record offsets stay relative to the member's base and the
+// 4 GiB rule of the 32-bit offsets is per member), dev_consts is [K][3].  Slots, compaction and records are the 1-D ensembles'; the kernels' member view
+// rebases gtab and dev_consts (member_view_grid) - there are no host-evaluated member constants, the source is the launch's.
+//
 // Source sets (geoac_set_sources: the fan's angles from n_src source points in one launch): a member is a (source, profile) pair, m = s K + k
 // with K the profiles of the atmosphere.  Slots, compaction and records are the ensembles' with M = n_src K members ([n_src][K][n_rays][legs][32]);
 // the tables stay per profile (member m reads profile m % K's), and mem_consts carries each member's source beside its profile's reference state.
@@ -193,6 +198,7 @@ struct GeoacDevParams {
     const double* mem_consts;       // [M][GEOAC_MEMC]: T_o, P_o, cbrt_To, c000 of the member's profile (host-evaluated as for a single profile), then src[3] and
                                     // src_trig[2] of its source (host libm, as for a single source)
     int           n_profiles;       // K: member tables in seg / rho / atab (member m reads table m % K)
+    long long     gtab_stride;      // grid ensembles: doubles from one member's table in gtab to the next (0 for a single grid); dev_consts is [K][3] then
 };
 
 #define GEOAC_MAXF      16      // frequencies of a set (GEOAC_MAX_FREQS)

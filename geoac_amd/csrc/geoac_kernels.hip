@@ -328,6 +328,16 @@ DEVINL int member_of_slot(const GeoacDevParams& P, int slot){
     const int m = __builtin_amdgcn_readfirstlane(slot) / P.mem_slots;
     return m < P.n_members ? m : P.n_members - 1;
 }
+// grid ensembles (geoac_upload_atmo_3d_ensemble): member m's evaluation table lies m gtab_stride doubles behind member 0's, its absorption reference state
+// (Eq3DRngDep::fan_init) in dev_consts[3 m ..]; nodes, source and every other parameter are the launch's.  With a wave-uniform m the table base stays in
+// scalar registers: the record offsets of the gathers (32-bit, relative to the member's base) and the LDS-DMA ring of grid_eval3_glds are addressed as for a single grid.
+DEVINL void member_view_grid(GeoacDevParams& P, int m){
+    P.gtab += (long long)m * P.gtab_stride;                       // (signed: k_postpass moves its view from member to member by the difference)
+    P.dev_consts += 3 * m;
+}
+template <class EQ> DEVINL void member_view_of(GeoacDevParams& P, int m){
+    if constexpr (EQ::SEG1D) member_view(P, m); else member_view_grid(P, m);
+}
 
 // ------------------------------------------------------------------------------------------------
 // Global equation set: fused GeoAc_UpdateSources + GeoAc_EvalSrcEq (EquationSets.Global.cpp:222-442),
@@ -1819,7 +1829,10 @@ template <class EQ, bool ENS = false>
 __global__ void __launch_bounds__(256) k_init(GeoacDevParams P){
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= P.n_pad) return;
-    if constexpr (ENS) member_view(P, member_of_slot(P, (int)(blockIdx.x * blockDim.x)));      // (S is a multiple of the workgroup)
+    if constexpr (ENS){
+        member_view_of<EQ>(P, member_of_slot(P, (int)(blockIdx.x * blockDim.x)));      // (S is a multiple of the workgroup)
+        if(i % P.mem_slots == 0) EQ::fan_init(P);                 // once per member, on the member's view (grid sets: its table, its slot of dev_consts)
+    } else
     if(i == 0) EQ::fan_init(P);
     double* st = P.state + i;
     const size_t np = (size_t)P.n_pad;
@@ -1911,9 +1924,12 @@ __global__ void __launch_bounds__(EQ::COOP ? 64 : 256, EQ::COOP ? GEOAC_COOP_WAV
     if constexpr (ENS){
         // every workgroup integrates rays of one member (member-major slots; the compacted list pads each member's columns to whole
         // workgroups): its first column names the member, whose table is then the one staged in LDS
-        static_assert(EQ::LANES == 1 && !EQ::COOP, "ensembles: one lane per ray, stratified sets");
+        // Grid sets: the same invariant is what the wave-cooperative gather stands on - the quads of a wave fetch each other's records from ONE table
+        // (grid_eval3_coop / _glds: offsets relative to the one base P.gtab).  It holds because S is a multiple of 256 (layout_angles), k_compact_ens pads
+        // each member's column range to the workgroup width (64 for these kernels) and the launch has no lane thinning (spread = 1).
+        static_assert(EQ::LANES == 1, "ensembles: one lane per ray");
         const int c0 = P.slot_lo + (int)(bidx * blockDim.x);
-        member_view(P, member_of_slot(P, (P.colmap && c0 < col_hi) ? P.colmap[c0] : c0));
+        member_view_of<EQ>(P, member_of_slot(P, (P.colmap && c0 < col_hi) ? P.colmap[c0] : c0));
     }
     const bool mine = !(P.spread > 1 && (tid0 & (P.spread - 1))) && col < col_hi;   // spread > 1: sparse lanes (grid sets, small fans)
     const int slot = (P.colmap && mine) ? P.colmap[col] : col;  // ray slot
@@ -2446,7 +2462,8 @@ DEVINL void pp_medium_by_key(const GeoacDevParams& P, char* wl, bool valid, unsi
 }
 
 template <class EQ, bool ENS = false>
-__global__ void __launch_bounds__(256, (ENS && EQ::PP_WAVES > 3) ? 3 : EQ::PP_WAVES) k_postpass(GeoacDevParams P, int rows){   // (ensembles: the member base pointers take two registers more)
+__global__ void __launch_bounds__(256, !ENS ? EQ::PP_WAVES : EQ::SEG1D ? (EQ::PP_WAVES > 3 ? 3 : EQ::PP_WAVES) : 2) k_postpass(GeoacDevParams P, int rows){   // (ensembles: the member base pointers take two registers more;
+    // grid ensembles: two waves per SIMD for both sets - at three the Cartesian kernel's member bookkeeping spills 17 more scalars than fit beside its 168 registers and 20 bytes go to scratch)
     // grid-stride sweep over (segment row i, ray slot); by default the grid covers the sweep in one pass
     // Grid sets (PP_TILE): a workgroup takes a tile of 16 rows x 16 rays, a wave 16 consecutive rows of 4 rays.  The segment midpoints of
     // one ray's consecutive rows lie in the same cell and vertical segment nearly always, so the 64 lanes of a table gather touch a handful
@@ -2455,6 +2472,7 @@ __global__ void __launch_bounds__(256, (ENS && EQ::PP_WAVES > 3) ? 3 : EQ::PP_WA
     const size_t np = (size_t)P.n_pad;
     const int bx = EQ::PP_TILE ? (P.n_cols_bound + 15) / 16 : (P.n_cols_bound + 255) / 256;      // column-blocks per row (tile row)
     const double* const seg0 = P.seg; const double* const rho0 = P.rho;      // (ensembles: the member tables' base)
+    int m_view = 0;                                               // grid ensembles: the member P is the view of (moved by differences: the bases themselves would cost four scalar registers)
     const long long total = (long long)bx * (EQ::PP_TILE ? (rows - 1 + 15) / 16 : rows - 1);
     for(long long w = blockIdx.x; w < total; w += gridDim.x){
         const int i = EQ::PP_TILE ? (int)(w / bx) * 16 + (int)((threadIdx.x & 63u) >> 2) : (int)(w / bx);
@@ -2467,6 +2485,15 @@ __global__ void __launch_bounds__(256, (ENS && EQ::PP_WAVES > 3) ? 3 : EQ::PP_WA
             // of the absorption at ground level under the midpoint: same cell, lowest segment - one or two keys per wave.
             extern __shared__ double pp_lds[];
             char* const wl = (char*)pp_lds + (threadIdx.x >> 6) * (GEOAC_PP_SLOTS * GEOAC_PP_SLOTB);
+            if constexpr (ENS){
+                // Grid ensembles: the keys of a wave are (cell, segment) pairs of ONE table, so a wave's four columns must belong to one member.  They do: a
+                // tile's 16 columns start at a multiple of 16, and every member's column range starts at a multiple of 64 - the slot ranges because S is a
+                // multiple of 256 (layout_angles), the compacted ranges because k_compact_ens pads each to the RK4 workgroup width (>= 64).  No tile straddles
+                // a member; the wave's first column names it (a padding column: the member's last slot).
+                const int c0 = (int)(w % bx) * 16 + (int)((threadIdx.x >> 6) << 2);
+                const int m = member_of_slot(P, (P.colmap && c0 < *P.n_cols) ? P.colmap[c0] : c0);
+                member_view_grid(P, m - m_view); m_view = m;
+            }
             const bool valid = (i < rows - 1) && col < (P.colmap ? *P.n_cols : P.n_pad) && (i + 1 < P.nrows[col < (int)np ? col : 0]);
             const double* a = P.path + ((size_t)(valid ? i : 0) * EQ::PW) * np + (valid ? col : 0);
             const double* b = a + (size_t)EQ::PW * np;
@@ -2505,8 +2532,8 @@ __global__ void __launch_bounds__(256, (ENS && EQ::PP_WAVES > 3) ? 3 : EQ::PP_WA
         double* o = P.contrib + ((size_t)i * 2) * np + col;
         double tt, at;
         if constexpr (ENS){                                       // (a wave's columns belong to one member; the block is viewed in place - a copy would go to scratch)
-            P.seg = seg0; P.rho = rho0;
-            member_view(P, member_of_slot(P, slot));
+            if constexpr (EQ::SEG1D){ P.seg = seg0; P.rho = rho0; member_view(P, member_of_slot(P, slot)); }
+            else { const int m = member_of_slot(P, slot); member_view_grid(P, m - m_view); m_view = m; }
         }
         EQ::segment(P, P.state + slot, np, a, b, tt, at);
         o[0]  = tt;
@@ -2926,7 +2953,7 @@ __global__ void __launch_bounds__(256) k_arrival(GeoacDevParams P){
     int slot, leg;
     if constexpr (ENS){                                           // grid y = member: the (slot, leg) pairs of member y's slot range
         if(id >= (long long)P.mem_slots * legs) return;
-        member_view(P, (int)blockIdx.y);
+        member_view_of<EQ>(P, (int)blockIdx.y);
         slot = (int)blockIdx.y * P.mem_slots + (int)(id / legs); leg = (int)(id % legs);
         if(P.perm[slot] < 0) return;                              // (slots without a ray)
     } else {
@@ -3275,7 +3302,7 @@ __global__ void __launch_bounds__(64) k_probe_grid(GeoacDevParams P, int n, cons
 // host-callable launchers (called from geoac_api.cpp)
 // ------------------------------------------------------------------------------------------------
 #ifndef GEOAC_NO_LAUNCHERS          // tools/dev_kernel.sh compiles single instantiations of the kernels above
-// ensembles: the stratified sets only (one-lane policies)
+// ensembles of the stratified sets (one-lane policies)
 #define GEOAC_DISPATCH_EQ_ENS(P, CALL) \
     switch((P)->eqset * 2 + ((P)->calc_amp ? 1 : 0)){ \
         case GEOAC_EQ_GLOBAL * 2 + 1: { using EQ = EqGlobal<true>;  CALL; } break; \
@@ -3285,6 +3312,17 @@ __global__ void __launch_bounds__(64) k_probe_grid(GeoacDevParams P, int n, cons
         case GEOAC_EQ_2D * 2 + 1:     { using EQ = Eq2D<true>;      CALL; } break; \
         case GEOAC_EQ_2D * 2 + 0:     { using EQ = Eq2D<false>;     CALL; } break; \
         default: return hipErrorNotSupported; }
+// ... and the grid sets' one-lane policies (geoac_upload_atmo_3d_ensemble): COOP matters to k_rk4 only
+#define GEOAC_DISPATCH_EQ_ENS_GRID(P, COOPF, CALL) \
+    switch((P)->eqset * 2 + ((P)->calc_amp ? 1 : 0)){ \
+        case GEOAC_EQ_3D_RNGDEP * 2 + 1:     { using EQ = Eq3DRngDep<true, 1, COOPF>;      CALL; } break; \
+        case GEOAC_EQ_3D_RNGDEP * 2 + 0:     { using EQ = Eq3DRngDep<false, 1, COOPF>;     CALL; } break; \
+        case GEOAC_EQ_GLOBAL_RNGDEP * 2 + 1: { using EQ = EqGlobalRngDep<true, 1, COOPF>;  CALL; } break; \
+        case GEOAC_EQ_GLOBAL_RNGDEP * 2 + 0: { using EQ = EqGlobalRngDep<false, 1, COOPF>; CALL; } break; \
+        default: return hipErrorNotSupported; }
+template <class EQ> struct IsGridOne { static constexpr bool v = false; };
+template <bool A, bool C> struct IsGridOne<Eq3DRngDep<A, 1, C, false>> { static constexpr bool v = true; };
+template <bool A, bool C> struct IsGridOne<EqGlobalRngDep<A, 1, C, false>> { static constexpr bool v = true; };
 template <class EQ> struct IsStrat { static constexpr bool v = false; };
 template <bool A> struct IsStrat<EqGlobal<A>> { static constexpr bool v = true; };
 template <bool A> struct IsStrat<Eq3D<A>> { static constexpr bool v = true; };
@@ -3359,6 +3397,7 @@ template <bool A> struct IsStrat<Eq2D<A>> { static constexpr bool v = true; };
 
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s){
     dim3 b(256), g((P->n_pad + 255) / 256);
+    if(P->n_members > 1 && P->gtab){ GEOAC_DISPATCH_EQ_ENS_GRID(P, false, hipLaunchKernelGGL((k_init<EQ, true>), g, b, 0, s, *P)); return hipGetLastError(); }
     if(P->n_members > 1){ GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_init<EQ, true>), g, b, 0, s, *P)); return hipGetLastError(); }
     GEOAC_DISPATCH_EQ(P, hipLaunchKernelGGL(k_init<EQ>, g, b, 0, s, *P));
     return hipGetLastError();
@@ -3397,6 +3436,13 @@ static hipError_t launch_rk4_t(const GeoacDevParams* P, int block, hipStream_t s
         if constexpr (IsStrat<EQ>::v){
             if(smp || (P->mem_slots % block) != 0 || (P->slot_lo % block) != 0) return hipErrorInvalidValue;
             if(P->table_in_lds) GEOAC_RK4_LAUNCH(true, false, , true); else GEOAC_RK4_LAUNCH(false, false, , true);
+            return hipGetLastError();
+        }
+        if constexpr (IsGridOne<EQ>::v){
+            // grid ensembles: no lane thinning (a workgroup's 64 lanes are 64 columns of one member), the table stays in memory
+            if(smp || P->spread > 1 || P->table_in_lds || (P->mem_slots % block) != 0 || (P->slot_lo % block) != 0) return hipErrorInvalidValue;
+            if(EQ::COOP && block != 64) return hipErrorInvalidValue;
+            GEOAC_RK4_LAUNCH(false, false, , true);
             return hipGetLastError();
         }
         return hipErrorNotSupported;
@@ -3466,7 +3512,11 @@ static hipError_t launch_rk4_trio(const GeoacDevParams*, hipStream_t, unsigned*)
 #endif
 extern "C" hipError_t geoac_launch_rk4(const GeoacDevParams* P, int block, hipStream_t s, unsigned* n_wg){
     if(P->n_members > 1){
-        if(P->duo || P->trio || P->lanes_per_ray != 1 || P->gtab) return hipErrorNotSupported;
+        if(P->duo || P->trio || P->lanes_per_ray != 1 || P->quad_cache) return hipErrorNotSupported;
+        if(P->gtab){
+            if(P->coop){ GEOAC_DISPATCH_EQ_ENS_GRID(P, true, return launch_rk4_t<EQ>(P, block, s, n_wg)); }
+            else { GEOAC_DISPATCH_EQ_ENS_GRID(P, false, return launch_rk4_t<EQ>(P, block, s, n_wg)); }
+        }
         GEOAC_DISPATCH_EQ_ENS(P, return launch_rk4_t<EQ>(P, block, s, n_wg));
     }
     if(P->duo) return launch_rk4_duo(P, s, n_wg);
@@ -3504,6 +3554,10 @@ extern "C" hipError_t geoac_launch_postpass(const GeoacDevParams* P, int rows, h
     if(nbl > 0x7fffffffLL) nbl = 0x7fffffffLL;
     int nb = (int)nbl;
     dim3 b(256), g(nb);
+    if(P->n_members > 1 && P->gtab){
+        GEOAC_DISPATCH_EQ_ENS_GRID(P, false, hipLaunchKernelGGL((k_postpass<EQ, true>), g, b, EQ::PP_DEDUP ? 4 * GEOAC_PP_SLOTS * GEOAC_PP_SLOTB : 0, s, *P, rows));
+        return hipGetLastError();
+    }
     if(P->n_members > 1){ GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_postpass<EQ, true>), g, b, 0, s, *P, rows)); return hipGetLastError(); }
     GEOAC_DISPATCH_EQ(P, hipLaunchKernelGGL(k_postpass<EQ>, g, b, EQ::PP_DEDUP ? 4 * GEOAC_PP_SLOTS * GEOAC_PP_SLOTB : 0, s, *P, rows));
     return hipGetLastError();
@@ -3634,6 +3688,7 @@ extern "C" hipError_t geoac_launch_arrival(const GeoacDevParams* P, hipStream_t 
     if(P->n_members > 1){
         if(!P->perm) return hipErrorInvalidValue;
         dim3 ge((unsigned)(((long long)P->mem_slots * (P->bounces + 1) + 255) / 256), (unsigned)P->n_members);
+        if(P->gtab){ GEOAC_DISPATCH_EQ_ENS_GRID(P, false, hipLaunchKernelGGL((k_arrival<EQ, true>), ge, b, 0, s, *P)); return hipGetLastError(); }
         GEOAC_DISPATCH_EQ_ENS(P, hipLaunchKernelGGL((k_arrival<EQ, true>), ge, b, 0, s, *P));
         return hipGetLastError();
     }

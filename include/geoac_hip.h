@@ -154,6 +154,20 @@ int  geoac_get_members(geoac_ctx* ctx, int* n_members);
  * radius [km]; xy_limits of geoac_params then hold GeoAc_lat_min/lat_max/lon_min/lon_max_limit [rad]. */
 int  geoac_upload_atmo_3d(geoac_ctx* ctx, int nx, int ny, int nz, const double* x, const double* y, const double* z,
                           const double* T, const double* u, const double* v, const double* rho);
+/* ensemble of K grids of profiles on the shared nodes x, y, z (GEOAC_EQ_3D_RNGDEP, GEOAC_EQ_GLOBAL_RNGDEP; 1 <= K <= GEOAC_MAX_MEMBERS): T, u, v, rho
+ * [K][nx][ny][nz] row-major, each member in the layout of geoac_upload_atmo_3d.  One geoac_fan_launch then integrates the fan's angles through every
+ * member; member m's records are bit-identical to those of a context that uploaded grid m alone and runs one lane per ray.  K = 1 is geoac_upload_atmo_3d.
+ * The device holds K evaluation tables (each the table of a plain upload of that grid): GEOAC_E_NOMEM when they do not fit in its free memory.  Once K > 1:
+ *   - geoac_fan_fetch, geoac_fan_records_dev and geoac_fan_copy_records_dev cover [K][n_rays][legs][GEOAC_REC_STRIDE], member-major;
+ *   - total_steps is the sum over the members;
+ *   - geoac_grid_table_fetch and the device-function probes (geoac_probe.h) evaluate member 0;
+ *   - geoac_fan_map, geoac_fan_stations and geoac_fan_tubemap work on the members as on those of a 1-D ensemble;
+ *   - sample capture (GEOAC_MODE_WRITE_RAYS / _CAUSTICS), geoac_clone, the eigenray searches, the pool, geoac_set_sources with n_src > 1 and
+ *     geoac_set_frequencies with n_freq > 1 return GEOAC_E_UNSUPPORTED, and so does geoac_fan_refine: its Newton rays start from a per-member medium
+ *     at the source, which the refinement's view of a context does not carry for grids.
+ * geoac_upload_atmo_3d sets K back to 1.  A stratified set returns GEOAC_E_UNSUPPORTED. */
+int  geoac_upload_atmo_3d_ensemble(geoac_ctx* ctx, int n_members, int nx, int ny, int nz, const double* x, const double* y, const double* z,
+                                   const double* T, const double* u, const double* v, const double* rho);
 /* the evaluation table the upload built on the device (geoac_grid_table_size(nx, ny, nz) doubles, layout of geoac_grid_table_eq in
  * geoac_host.h, which is the host restatement of the same construction): set-up check / diagnostics */
 int  geoac_grid_table_fetch(geoac_ctx* ctx, double* tab, size_t cap);
