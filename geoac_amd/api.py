@@ -712,7 +712,13 @@ class FanContext:
     def timing(self):
         ms = (ctypes.c_double * 3)(); st = (ctypes.c_uint64 * 3)()
         self._chk(self.lib.geoac_last_timing(self._h, ms, st))
-        return dict(ms_total=ms[0], ms_rk4=ms[1], ms_post=ms[2], epochs=int(st[0]), path_bytes_w=int(st[1]), path_bytes_r=int(st[2]))
+        t = dict(ms_total=ms[0], ms_rk4=ms[1], ms_post=ms[2], epochs=int(st[0]), path_bytes_w=int(st[1]), path_bytes_r=int(st[2]))
+        # ms_wait: between the RK4 epochs (geoac_last_wait).  A library named by GEOAC_LIB that was built before the export existed has no such key
+        if hasattr(self.lib, "geoac_last_wait"):
+            w = ctypes.c_double(0.0)
+            self._chk(self.lib.geoac_last_wait(self._h, ctypes.byref(w)))
+            t["ms_wait"] = w.value
+        return t
 
     # ---- eigenray searches (include/geoac_eig.h), spherical sets ----
     def _eig_collect(self, res):

@@ -46,7 +46,7 @@ extern "C" hipError_t geoac_launch_probe_absorption(const GeoacDevParams* P, int
 extern "C" hipError_t geoac_launch_probe_atab(const GeoacDevParams* P, int n, const double* x, double* out, hipStream_t s);
 extern "C" hipError_t geoac_launch_probe_grid(const GeoacDevParams* P, int n, const double* a0, const double* a1, const double* a2, int coop,
                                               double* out30, double* api7, hipStream_t s);
-extern "C" hipError_t geoac_launch_gate(const GeoacDevParams* P, unsigned long long expected, hipStream_t s);
+extern "C" hipError_t geoac_launch_gate(const GeoacDevParams* P, unsigned long long expected, int delay_ms, hipStream_t s);
 extern "C" hipError_t geoac_launch_postpass(const GeoacDevParams* P, int rows, hipStream_t s);
 extern "C" hipError_t geoac_launch_postpass_tab(const GeoacDevParams* P, int rows, hipStream_t s);
 extern "C" hipError_t geoac_launch_atab_build(const GeoacDevParams* P, double* tab, double tol, hipStream_t s);
@@ -124,6 +124,7 @@ struct geoac_ctx {
     unsigned long long src_gen_at_clone = 0;                       // ... and its value when the clone was made
     unsigned long long sticky_flags = 0;   // GEOAC_FAN_*_FALLBACK: plan features this context has withdrawn after a failed attempt (geoac_fan_status)
     int  launch_repeats = 0;         // fans that were run a second time for that reason
+    int  pp_test_delay_ms = 0;       // PP_TEST_DELAY_MS (tests): k_gate holds the post-pass stream that many ms longer in every epoch - a late post-pass for the chunk-reuse edges (fan_launch_once)
     bool sub_test_stall = false;     // SUB_TEST_STALL (tests): the cooperative grid kernels' workgroups of sub-epoch 0 do not publish their flag - forces the hand-off time-out
     int  pp_onetrip = -1;            // table post-pass: record + table entry of the neighbouring segment in one trip (PP_ONETRIP; < 0: every fan but the hybrid ones)
     bool tile_rays = true;           // grid sets: Z-order over (inclination, azimuth) ranks instead of the inclination order (GEOAC_TILE=0)
@@ -137,7 +138,7 @@ struct geoac_ctx {
     int  grid_lanes = 0;             // GEOAC_GRID_LANES=1|2|4: force the lanes-per-ray variant of the grid kernels (tests); 0 = by fan size
     int  spread_override = 0;        // GEOAC_SPREAD=n: force n-way lane thinning of the grid-set RK4 waves (1 = dense); 0 = automatic
     bool compact = true;             // GEOAC_COMPACT=0: every epoch runs over all slots (no live-ray compaction between epochs)
-    DevBuf colmap[3], ncols;         // per chunk: column -> slot list of the rays alive at the start of that epoch; their counts (3 ints)
+    DevBuf colmap[6], ncols;         // per set of small arrays (below): column -> slot list of the rays alive at the start of that epoch; their counts (8 ints)
     bool quad_cache = true;          // GEOAC_QUAD_CACHE=0: four-lane grid kernels without the per-lane record cache (A/B)
     int  sub_min_waves = 1024;       // GEOAC_SUB_MIN_WAVES: smallest launch (waves) that is cut into sub-epochs (tests lower it to cover the hand-off with small fans)
     int  sub_epochs = 4;             // GEOAC_SUB_EPOCHS: sub-epochs of the cooperative grid kernels when a fan has more waves than the chip has wave slots (k_rk4); 1 = off
@@ -160,7 +161,8 @@ struct geoac_ctx {
     bool have_grid = false;
     // device
     DevBuf seg, rhot, theta, phi, state, rec, counters;
-    DevBuf path[3], contrib[3], nrows[3], legend[3], nlegend[3];   // epoch chunks, two or three in rotation (RK4 of epoch e+1 overlaps the post-pass of e)
+    DevBuf path[3], contrib[3];                                     // epoch chunks, two or three in rotation (RK4 of epoch e+1 overlaps the post-pass of e)
+    DevBuf nrows[6], legend[6], nlegend[6];                         // the small per-epoch arrays: a rotation of their own, n or 2 n sets (fan_launch_once, epoch pipeline)
     hipStream_t pp_stream = nullptr;                                // post-pass stream
     hipStream_t acc_stream = nullptr;                               // k_accum stream
     std::vector<hipEvent_t> evp;                                    // per epoch: k_postpass has finished (k_accum may start)
@@ -172,7 +174,7 @@ struct geoac_ctx {
     unsigned long long* h_counters = nullptr;     // pinned
     int n_rays = 0, n_pad = 0, legs = 0;
     // last launch
-    double ms_total = 0, ms_rk4 = 0, ms_post = 0;
+    double ms_total = 0, ms_rk4 = 0, ms_post = 0, ms_wait = 0;
     unsigned long long n_epochs = 0, path_bytes_w = 0, path_bytes_r = 0, total_steps = 0, err_flags = 0;
     int s_rows_override = 0;
     bool no_overlap = false;                      // GEOAC_NO_OVERLAP=1: post-pass on the RK4 stream (diagnostics)
@@ -184,6 +186,8 @@ struct geoac_ctx {
                                                   // long ones - that get a whole epoch's rows per launch while the others get stagger_rows of them (STAGGER_FRAC; 0: off; < 0: by launch plan)
     double stagger_rows = -1.0;                   // ... STAGGER_ROWS (< 0: by launch plan)
     double hybrid_rows = -1.0;                    // hybrid fans: rows per epoch of the one-lane launch relative to the two-lane launch (HYBRID_ROWS; < 0: the set's own default, plan_hybrid_rows)
+    double accum_batch_live = -1.0;               // ACCUM_BATCH_LIVE=f: hybrid fans batch the sums (ACCUM_BATCH) from the epoch on at whose launch at most the share f of the rays was alive; < 0: by launch plan
+    bool reuse_edges = true;                      // REUSE_EDGES=0: a path chunk is reused only after k_accum of its previous epoch, for every fan (A/B measurements; default: after its post-pass where the data allow, fan_launch_once)
     bool two_chunks = false;                      // GEOAC_TWO_CHUNKS=1: two path chunks in rotation instead of three (A/B measurements)
     bool trace_epochs = false;                    // GEOAC_TRACE_EPOCHS=1: per-epoch live counts on stderr
     bool no_gate = false;                         // GEOAC_NO_GATE=1: post-pass not held back behind the next RK4 launch (A/B measurements)
@@ -413,8 +417,8 @@ extern "C" void geoac_probe_step_horizon(const double* hz, int n, const double* 
 
 // ---- launch-plan options (A/B measurements, tests; results never depend on them) ----
 static const char* const kOptionNames[] = {
-    "S_ROWS", "NO_OVERLAP", "PP_BLOCKS", "ABS_TABLE", "ABS_TABLE_TOL", "PPFIX_CAP", "DUO", "TRIO", "EV_SLACK", "NO_PAIR", "PAIR_FRAC", "HYBRID_ROWS", "STAGGER_FRAC", "STAGGER_ROWS", "TWO_CHUNKS", "TRACE_EPOCHS", "NO_GATE", "SORT", "TILE", "PP_ONETRIP", "PP_LDS_TABLE", "PP_LDS_PAD", "CU_SPLIT", "CHUNK_GIB", "ACCUM_BATCH",
-    "NO_QUAD", "GRID_LANES", "OCT", "HEX", "SPREAD", "COMPACT", "QUAD_CACHE", "GRID_COOP", "SUB_EPOCHS", "SUB_MIN_WAVES", "SUB_TEST_STALL", "SMP_CAP", "GRID_BUILD", "RANGE_SKIP", "POLE_FAST", nullptr };
+    "S_ROWS", "NO_OVERLAP", "PP_BLOCKS", "ABS_TABLE", "ABS_TABLE_TOL", "PPFIX_CAP", "DUO", "TRIO", "EV_SLACK", "NO_PAIR", "PAIR_FRAC", "HYBRID_ROWS", "STAGGER_FRAC", "STAGGER_ROWS", "TWO_CHUNKS", "REUSE_EDGES", "ACCUM_BATCH_LIVE", "TRACE_EPOCHS", "NO_GATE", "SORT", "TILE", "PP_ONETRIP", "PP_LDS_TABLE", "PP_LDS_PAD", "CU_SPLIT", "CHUNK_GIB", "ACCUM_BATCH",
+    "NO_QUAD", "GRID_LANES", "OCT", "HEX", "SPREAD", "COMPACT", "QUAD_CACHE", "GRID_COOP", "SUB_EPOCHS", "SUB_MIN_WAVES", "SUB_TEST_STALL", "PP_TEST_DELAY_MS", "SMP_CAP", "GRID_BUILD", "RANGE_SKIP", "POLE_FAST", nullptr };
 const char* const* geoac_option_names(void){ return kOptionNames; }
 
 int geoac_set_option(geoac_ctx* ctx, const char* key, const char* value){
@@ -454,6 +458,8 @@ int geoac_set_option(geoac_ctx* ctx, const char* key, const char* value){
     else if(k == "STAGGER_ROWS"){ if(!dbl_ok || !(dv > 0.0 && dv <= 1.0)) return bad("a ratio in (0, 1]"); ctx->stagger_rows = dv; }
     else if(k == "HYBRID_ROWS"){ if(!dbl_ok || !(dv > 0.0 && dv <= 1.0)) return bad("a ratio in (0, 1]"); ctx->hybrid_rows = dv; }
     else if(k == "TWO_CHUNKS") return flag(ctx->two_chunks);
+    else if(k == "REUSE_EDGES") return flag(ctx->reuse_edges);
+    else if(k == "ACCUM_BATCH_LIVE"){ if(!dbl_ok || dv < -1.0 || dv > 1.0) return bad("a share in [0, 1] (0: never), or -1 (by launch plan)"); ctx->accum_batch_live = dv; }
     else if(k == "RANGE_SKIP") return flag(ctx->range_skip);
     else if(k == "POLE_FAST") return flag(ctx->pole_fast);
     else if(k == "TRACE_EPOCHS") return flag(ctx->trace_epochs);
@@ -481,6 +487,7 @@ int geoac_set_option(geoac_ctx* ctx, const char* key, const char* value){
     else if(k == "SUB_EPOCHS"){ if(!int_ok || lv < 1 || lv > 16) return bad("1..16"); ctx->sub_epochs = iv; }
     else if(k == "SUB_MIN_WAVES"){ if(!int_ok || lv < 0 || lv > 0x7fffffff) return bad("a wave count >= 0"); ctx->sub_min_waves = iv; }
     else if(k == "SUB_TEST_STALL") return flag(ctx->sub_test_stall);
+    else if(k == "PP_TEST_DELAY_MS"){ if(!int_ok || lv < 0 || lv > 50) return bad("milliseconds in 0 .. 50"); ctx->pp_test_delay_ms = iv; }
     else if(k == "SMP_CAP"){ if(!int_ok || lv <= 0) return bad("a row capacity > 0"); ctx->smp_cap = lv; }
     else if(k == "GRID_BUILD"){ if(strcmp(value, "host") != 0 && strcmp(value, "device") != 0) return bad("host or device"); ctx->grid_build_host = (strcmp(value, "host") == 0); }
     else return fail(ctx, GEOAC_E_INVALID, "set_option: unknown key " + k);
@@ -537,13 +544,12 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->rfn_state){ geoac_rfn_release(ctx->rfn_state); ctx->rfn_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
-                       &ctx->nrows[0], &ctx->nrows[1], &ctx->nrows[2], &ctx->legend[0], &ctx->legend[1], &ctx->legend[2],
-                       &ctx->nlegend[0], &ctx->nlegend[1], &ctx->nlegend[2],
                        &ctx->ev_row[0], &ctx->ev_row[1], &ctx->ev_row[2], &ctx->ev_m[0], &ctx->ev_m[1], &ctx->ev_m[2],
                        &ctx->ev_amp[0], &ctx->ev_amp[1], &ctx->ev_amp[2], &ctx->nev[0], &ctx->nev[1], &ctx->nev[2], &ctx->smp_out,
-                       &ctx->d_gx, &ctx->d_gy, &ctx->d_gz, &ctx->d_gtab, &ctx->d_gtab8, &ctx->d_consts, &ctx->sub_flags, &ctx->colmap[0], &ctx->colmap[1], &ctx->colmap[2], &ctx->ncols, &ctx->atab, &ctx->ppfix,
+                       &ctx->d_gx, &ctx->d_gy, &ctx->d_gz, &ctx->d_gtab, &ctx->d_gtab8, &ctx->d_consts, &ctx->sub_flags, &ctx->ncols, &ctx->atab, &ctx->ppfix,
                        &ctx->fcontrib[0], &ctx->fcontrib[1], &ctx->fcontrib[2], &ctx->fstate, &ctx->fatten, &ctx->ffix, &ctx->fcnt };
     for(DevBuf* b : bufs) b->release();
+    for(int b = 0; b < 6; b++){ ctx->nrows[b].release(); ctx->legend[b].release(); ctx->nlegend[b].release(); ctx->colmap[b].release(); }
     g_deferred.drain();
     if(ctx->h_counters) hipHostFree(ctx->h_counters);
     if(ctx->ev0) hipEventDestroy(ctx->ev0);
@@ -591,7 +597,7 @@ int geoac_clone(geoac_ctx* src, geoac_ctx** out){
         hipError_t e = c->d_consts.ensure(sizeof(double) * 8);
         if(e != hipSuccess){ geoac_destroy(c); return hipfail(src, e, "clone: constants block"); }
     }
-    c->sort_rays = src->sort_rays; c->tile_rays = src->tile_rays; c->pp_onetrip = src->pp_onetrip; c->pp_lds_table = src->pp_lds_table; c->pp_lds_pad = src->pp_lds_pad; c->cu_split = src->cu_split; c->chunk_gib = src->chunk_gib; c->accum_batch = src->accum_batch; c->sub_test_stall = src->sub_test_stall; c->no_quad = src->no_quad; c->oct = src->oct; c->hex = src->hex; c->grid_lanes = src->grid_lanes; c->spread_override = src->spread_override;
+    c->sort_rays = src->sort_rays; c->tile_rays = src->tile_rays; c->pp_onetrip = src->pp_onetrip; c->pp_lds_table = src->pp_lds_table; c->pp_lds_pad = src->pp_lds_pad; c->cu_split = src->cu_split; c->chunk_gib = src->chunk_gib; c->accum_batch = src->accum_batch; c->sub_test_stall = src->sub_test_stall; c->pp_test_delay_ms = src->pp_test_delay_ms; c->reuse_edges = src->reuse_edges; c->accum_batch_live = src->accum_batch_live; c->no_quad = src->no_quad; c->oct = src->oct; c->hex = src->hex; c->grid_lanes = src->grid_lanes; c->spread_override = src->spread_override;
     c->compact = src->compact; c->quad_cache = src->quad_cache; c->sub_min_waves = src->sub_min_waves; c->sub_epochs = src->sub_epochs; c->grid_coop = src->grid_coop;
     c->smp_cap = src->smp_cap; c->s_rows_override = src->s_rows_override; c->no_overlap = src->no_overlap; c->pp_blocks = src->pp_blocks; c->pair_frac = src->pair_frac; c->stagger_frac = src->stagger_frac; c->stagger_rows = src->stagger_rows;
     c->hybrid_rows = src->hybrid_rows; c->two_chunks = src->two_chunks; c->no_gate = src->no_gate; c->no_pair = src->no_pair; c->duo = src->duo; c->trio = src->trio; c->abs_table = src->abs_table;
@@ -1346,12 +1352,22 @@ static int fan_launch_once(geoac_ctx* ctx){
     bool late_pair = false;
     unsigned long long long_bound = (unsigned long long)(plan_stagger_frac * ctx->n_rays);      // live rays of the leading share (an upper bound: what its last launch counted)
     if(compact){
-        for(int b = 0; b < 3; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * ((size_t)P.n_pad + M)));      // (ensembles: + the members' range starts)
-        HIPCHK(ctx->ncols.ensure(4 * sizeof(int)));
+        HIPCHK(ctx->ncols.ensure(8 * sizeof(int)));
     }
     P.n_cols_bound = P.n_pad;
     P.sub = 1; P.sub_w = 0; P.sub_flags = nullptr;
     const int n_chunks = ctx->two_chunks ? 2 : 3;     // three path chunks in rotation: the post-pass may lag the RK4 by more than one epoch (measured: GeoAc3D 360 x 90 fan 212 -> 160 ms; GEOAC_TWO_CHUNKS=1 for A/B)
+    // Chunk reuse follows the data (stratified sets, arrivals only, one frequency; see the epoch loop): k_rk4(e) waits for the post-pass of epoch e - n alone, and
+    // the small per-epoch arrays, which k_accum(e - n) may still be reading then, rotate over 2 n sets of their own.  Sample capture (k_accum reads path rows and the
+    // event lists), frequency sets (fcontrib, k_accum_freq) and the grid sets keep one rotation of n for everything and the wait for k_accum(e - n).
+    const bool data_edges = !is_grid && !sampling && F == 1 && !ctx->no_overlap && ctx->reuse_edges;      // (REUSE_EDGES=0: the wait for k_accum for every fan, A/B)
+    const int n_small = data_edges ? 2 * n_chunks : n_chunks;
+    if(compact) for(int b = 0; b < n_small; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * ((size_t)P.n_pad + M)));      // (ensembles: + the members' range starts)
+    for(int b = 0; b < n_small; b++){
+        HIPCHK(ctx->nrows[b].ensure(sizeof(int) * (size_t)P.n_pad));
+        HIPCHK(ctx->nlegend[b].ensure(sizeof(int) * (size_t)P.n_pad));
+        HIPCHK(ctx->legend[b].ensure(sizeof(int) * (size_t)P.n_pad * GEOAC_MAXLEGS));
+    }
     for(int b = 0; b < n_chunks; b++){
         if(sampling){                                             // per-chunk event lists of the WriteRays / WriteCaustics rows
             HIPCHK(ctx->ev_row[b].ensure(sizeof(int) * (size_t)P.ev_cap * P.n_pad));
@@ -1359,9 +1375,6 @@ static int fan_launch_once(geoac_ctx* ctx){
             HIPCHK(ctx->ev_amp[b].ensure(sizeof(double) * (size_t)P.ev_cap * P.n_pad));
             HIPCHK(ctx->nev[b].ensure(sizeof(int) * (size_t)P.n_pad));
         }
-        HIPCHK(ctx->nrows[b].ensure(sizeof(int) * (size_t)P.n_pad));
-        HIPCHK(ctx->nlegend[b].ensure(sizeof(int) * (size_t)P.n_pad));
-        HIPCHK(ctx->legend[b].ensure(sizeof(int) * (size_t)P.n_pad * GEOAC_MAXLEGS));
     }
 
     // the path chunks themselves.  The free-memory figure above can be stale by the time they are allocated (another process on the same
@@ -1448,7 +1461,11 @@ static int fan_launch_once(geoac_ctx* ctx){
         GeoacFreqParams Qq = Q;
         if(F > 1) Qq.contrib = (double*)ctx->fcontrib[e % (size_t)n_chunks].p;
         HIPCHK(hipStreamWaitEvent(sp, ctx->evs[4 * e + 1], 0));
-        if(gate_expected > 0 && sp != s && !ctx->no_gate && !cu_split) HIPCHK(geoac_launch_gate(&Pq, gate_expected, sp));
+        // k_postpass(e) writes contrib[e % n], which k_accum(e - n) reads (without data_edges that order follows from k_rk4(e)'s wait for k_accum(e - n)).  Recorded by
+        // enqueue_post(e - n), n calls before this one
+        if(data_edges && e >= (size_t)n_chunks) HIPCHK(hipStreamWaitEvent(sp, ctx->evs[4 * (e - n_chunks) + 3], 0));
+        {   const bool gated = gate_expected > 0 && !ctx->no_gate && !cu_split;
+            if(sp != s && (gated || ctx->pp_test_delay_ms > 0)) HIPCHK(geoac_launch_gate(&Pq, gated ? gate_expected : 0ull, ctx->pp_test_delay_ms, sp)); }
         HIPCHK(hipEventRecord(ctx->evs[4 * e + 2], sp));
         if(Pq.atab_on){
             // (see geoac_launch_postpass_tab) hybrid fans: the post-pass off the RK4 CUs, one (spherical set) or two (Cartesian sets) workgroups per free CU
@@ -1505,19 +1522,35 @@ static int fan_launch_once(geoac_ctx* ctx){
         while(ctx->evj.size() < 2 * e + 2){ hipEvent_t ev; HIPCHK(hipEventCreate(&ev)); ctx->evj.push_back(ev); }
         GeoacDevParams Pe = P;
         Pe.s_rows = rows_now;
-        Pe.accum_batch = (ctx->accum_batch >= 0) ? (ctx->accum_batch ? 1 : 0) : (((rows_now == rows_late && rows_late != P.s_rows) || stagger_plan) ? 1 : 0);   // (few waves alive: the sums are the tail; staggered fans: measured 0-2 % faster in every epoch)
+        // hybrid fans: the sums are batched once the fan has begun to thin out (live_bound: the rays alive after epoch e - 2).  With the chunks reused behind the post-pass the
+        // RK4 launches no longer wait for the sums, and the pass ends behind k_accum of the last full epochs instead (5 - 7 ms each, one after the other).  Batched in EVERY
+        // epoch they take 1.5 ms per pass from the RK4 launches they run beside (metric fan: 112.1 ms against 112.7 without); from the first epoch after rays have finished
+        // on - epoch 4 of 9 - 110.9 ms.  The spherical set's plan; the 3-D set's hybrid fans (config 2) were measured slower with ACCUM_BATCH=1 and not with a share.
+        const double plan_batch_live = ctx->accum_batch_live >= 0.0 ? ctx->accum_batch_live : (is_global ? 0.9 : 0.0);
+        const bool batch_thinned = hybrid && plan_batch_live > 0.0 && (double)live_bound <= plan_batch_live * ctx->n_rays;
+        Pe.accum_batch = (ctx->accum_batch >= 0) ? (ctx->accum_batch ? 1 : 0) : (((rows_now == rows_late && rows_late != P.s_rows) || stagger_plan || batch_thinned) ? 1 : 0);   // (few waves alive: the sums are the tail; staggered fans: measured 0-2 % faster in every epoch)
         if(late_pair) Pe.lanes_per_ray = 2;
         Pe.path = (double*)ctx->path[b].p; Pe.contrib = (double*)ctx->contrib[b].p;
-        Pe.nrows = (int*)ctx->nrows[b].p; Pe.legend = (int*)ctx->legend[b].p; Pe.nlegend = (int*)ctx->nlegend[b].p;
+        const int sb = (int)(e % (size_t)n_small);            // this epoch's set of the small arrays
+        Pe.nrows = (int*)ctx->nrows[sb].p; Pe.legend = (int*)ctx->legend[sb].p; Pe.nlegend = (int*)ctx->nlegend[sb].p;
         if(sampling){ Pe.ev_row = (int*)ctx->ev_row[b].p; Pe.ev_m = (int*)ctx->ev_m[b].p; Pe.ev_amp = (double*)ctx->ev_amp[b].p; Pe.nev = (int*)ctx->nev[b].p; }
-        if(e >= (size_t)n_chunks) HIPCHK(hipStreamWaitEvent(s, ctx->evs[4 * (e - n_chunks) + 3], 0));      // chunk b free again?
+        // ---- chunk b free again?  Every wait names an event that an EARLIER call of enqueue_post has already recorded, in host program order: a wait on an event
+        //      not yet recorded (in this launch) is no wait at all - it passes at once, or sees the state a previous launch left - and nothing would say so.
+        //      enqueue_post(x) runs in iteration x + 1 and records evs[4x + 2], evp[x], evs[4x + 3]; iteration e names x = e - n <= e - 2 here (n = 2: recorded in
+        //      iteration e - 1), and enqueue_post(e) names x = e - n, recorded n calls earlier.
+        //      data_edges: k_rk4(e) (and the one-lane launch beside it, which waits for evs[4e] below) overwrites path[b], read last by k_postpass_tab / k_ppfix /
+        //      k_postpass(e - n): the wait is for evp[e - n].  contrib[b] is written by k_postpass(e) alone, which waits for k_accum(e - n) itself (enqueue_post).
+        //      The small arrays of set e % 2n were read last by k_accum(e - 2n): that has finished, because k_postpass(e - n) did not start before evs[4(e - 2n) + 3]
+        //      and k_rk4(e) does not start before k_postpass(e - n) has ended - so 2 n sets suffice.
+        //      Otherwise (sample capture, frequency sets, grid sets, one stream): everything of epoch e - n, k_accum included. ----
+        if(e >= (size_t)n_chunks) HIPCHK(hipStreamWaitEvent(s, data_edges ? ctx->evp[e - n_chunks] : ctx->evs[4 * (e - n_chunks) + 3], 0));
         if(compact && e >= 1){
             // columns of this epoch = rays alive after the previous one; the launch is sized by the newest live count the host has
             // (after epoch e-2: an upper bound), lanes beyond the device-side count leave at once
-            const int pb = (int)((e - 1) % (size_t)n_chunks);
+            const int pb = (int)((e - 1) % (size_t)n_small);
             HIPCHK(geoac_launch_compact(&P, e == 1 ? nullptr : (const int*)ctx->colmap[pb].p, (const int*)ctx->ncols.p + pb, P.n_pad,
-                                        (int*)ctx->colmap[b].p, (int*)ctx->ncols.p + b, block, s));
-            Pe.colmap = (const int*)ctx->colmap[b].p; Pe.n_cols = (const int*)ctx->ncols.p + b;
+                                        (int*)ctx->colmap[sb].p, (int*)ctx->ncols.p + sb, block, s));
+            Pe.colmap = (const int*)ctx->colmap[sb].p; Pe.n_cols = (const int*)ctx->ncols.p + sb;
             // (ensembles: each member's columns padded to whole workgroups)
             Pe.n_cols_bound = (int)std::min<unsigned long long>((unsigned long long)P.n_pad, (live_bound + 63ull) / 64ull * 64ull + (ens ? (unsigned long long)M * block : 0ull));
             if(Pe.n_cols_bound < 64) Pe.n_cols_bound = 64;
@@ -1625,12 +1658,14 @@ static int fan_launch_once(geoac_ctx* ctx){
 
     float ms = 0; hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
     ctx->ms_total = ms;
-    ctx->ms_rk4 = 0; ctx->ms_post = 0;
+    ctx->ms_rk4 = 0; ctx->ms_post = 0; ctx->ms_wait = 0;
     for(size_t e = 0; e < (size_t)ctx->n_epochs; e++){
-        float a = 0, b = 0;
+        float a = 0, b = 0, w = 0;
         hipEventElapsedTime(&a, ctx->evs[4 * e], ctx->evs[4 * e + 1]);
         hipEventElapsedTime(&b, ctx->evs[4 * e + 2], ctx->evs[4 * e + 3]);
-        ctx->ms_rk4 += a; ctx->ms_post += b;
+        // between the RK4 launches: the end of one epoch's to the start of the next one's - the wait for the chunk, the compaction, the counters' memsets
+        if(e >= 1) hipEventElapsedTime(&w, ctx->evs[4 * (e - 1) + 1], ctx->evs[4 * e]);
+        ctx->ms_rk4 += a; ctx->ms_post += b; ctx->ms_wait += w;
     }
     ctx->total_steps = ctx->h_counters[8 + 0];
     ctx->err_flags = ctx->h_counters[8 + 2];
@@ -1955,6 +1990,12 @@ int geoac_last_timing(geoac_ctx* ctx, double ms[3], uint64_t stats[3]){
     if(!ctx || !ctx->ran) return GEOAC_E_INVALID;
     if(ms){ ms[0] = ctx->ms_total; ms[1] = ctx->ms_rk4; ms[2] = ctx->ms_post; }
     if(stats){ stats[0] = ctx->n_epochs; stats[1] = ctx->path_bytes_w; stats[2] = ctx->path_bytes_r; }
+    return GEOAC_OK;
+}
+
+int geoac_last_wait(geoac_ctx* ctx, double* ms_wait){
+    if(!ctx || !ctx->ran || !ms_wait) return GEOAC_E_INVALID;
+    *ms_wait = ctx->ms_wait;
     return GEOAC_OK;
 }
 

@@ -3532,16 +3532,22 @@ extern "C" hipError_t geoac_launch_rk4(const GeoacDevParams* P, int block, hipSt
 // refill every CU as fast as they drain, and an RK4 workgroup (a whole CU: 153 KB of LDS, 4 x 384 registers) is then not placed before
 // the post-pass grid is exhausted - the epoch degenerates to post-pass followed by RK4.  With the gate the RK4 workgroups take their CUs
 // first and the post-pass fills what is left.  Bounded spin (~40 ms): the gate always exits, a late RK4 launch only costs the ordering.
-__global__ void __launch_bounds__(64) k_gate(const unsigned long long* counter, unsigned long long expected){
+// delay_ticks > 0 (tests, PP_TEST_DELAY_MS): behind the gate the stream is held that many ticks of the 100 MHz wall clock longer, then goes on - a late post-pass
+// for the tests of the chunk-reuse edges (geoac_api.cpp).  It waits for the clock alone, and the loop has a trip bound of its own.
+__global__ void __launch_bounds__(64) k_gate(const unsigned long long* counter, unsigned long long expected, long long delay_ticks){
     if(threadIdx.x != 0) return;
     for(int it = 0; it < 20000; it++){
         if(__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= expected) break;
         __builtin_amdgcn_s_sleep(64);
     }
+    if(delay_ticks > 0){
+        const long long t0 = wall_clock64();
+        for(int it = 0; it < 400000 && wall_clock64() - t0 < delay_ticks; it++) __builtin_amdgcn_s_sleep(16);
+    }
 }
 
-extern "C" hipError_t geoac_launch_gate(const GeoacDevParams* P, unsigned long long expected, hipStream_t s){
-    hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, s, (const unsigned long long*)(P->counters + 5), expected);
+extern "C" hipError_t geoac_launch_gate(const GeoacDevParams* P, unsigned long long expected, int delay_ms, hipStream_t s){
+    hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, s, (const unsigned long long*)(P->counters + 5), expected, (long long)delay_ms * 100000ll);
     return hipGetLastError();
 }
 

@@ -279,6 +279,9 @@ int  geoac_fan_run(geoac_ctx* ctx, int n_rays, const double* theta_deg, const do
 /* HIP-event timings of the last completed launch, in ms: [0] whole launch, [1] RK4 kernels, [2] post-pass kernels;
  * and launch statistics: [0] rk4 kernel launches, [1] path bytes written, [2] path bytes read */
 int  geoac_last_timing(geoac_ctx* ctx, double ms[3], uint64_t stats[3]);
+/* ... and the time between its RK4 epochs, in ms: summed over the epochs, from the end of one epoch's RK4 launches to the start of the next one's (what the
+ * RK4 stream spent waiting for a path chunk to come free, plus the few small launches between two epochs) */
+int  geoac_last_wait(geoac_ctx* ctx, double* ms_wait);
 
 const char* geoac_strerror(int code);
 const char* geoac_last_error(geoac_ctx* ctx);
