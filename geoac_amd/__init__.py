@@ -12,4 +12,5 @@ from .api import (  # noqa: F401
     StationSpec, station_spec, station_check, STA, STA_STRIDE,
     RefineSpec, refine_spec, refine_check, RFN, RFN_STRIDE, RFN_STATUS, RFN_MAX_RAY_MEMBERS,
     TubeSpec, tube_spec, tube_check, TUBE, TUBE_MAX_SPAN, TUBE_COOP_MIN,
+    levels_check, LVL, LVL_STRIDE, MAX_LEVELS,
 )

@@ -58,6 +58,20 @@ def map_check(eqset, spec):
     return int(cells.value)
 
 
+MAX_LEVELS, LVL_STRIDE = 8, 12
+LVL = dict(LEG=0, DIR=1, FRAC=2, TTIME=3, ATTEN=4, P0=5)      # a crossing record (include/geoac_levels.h)
+
+
+def levels_check(eqset, params, z_km, cap=8):
+    """geoac_levels_check: host-only validation of a level list against `params` (no GPU needed); raises GeoAcError with the status and the fault"""
+    lib = load_library()
+    z = _arr(z_km).reshape(-1)
+    fault = ctypes.c_char_p()
+    rc = lib.geoac_levels_check(int(eqset), ctypes.byref(params), len(z), _p(z) if len(z) else None, int(cap), ctypes.byref(fault))
+    if rc:
+        raise GeoAcError(f"geoac_levels_check: {lib.geoac_strerror(rc).decode()}: {fault.value.decode() if fault.value else ''}")
+
+
 class StationSpec(ctypes.Structure):
     """geoac_station_spec (include/geoac_stations.h): lattice of the launch angles, filters and list length of a station search"""
     _fields_ = [("n_theta", ctypes.c_int), ("n_phi", ctypes.c_int), ("phi_periodic", ctypes.c_int), ("leg_min", ctypes.c_int), ("leg_max", ctypes.c_int),
@@ -496,6 +510,39 @@ class FanContext:
                 raise GeoAcError(f"fetch_atten(out=): need a C-contiguous float64 array of shape {shape}")
         self._chk(self.lib.geoac_fan_fetch_atten(self._h, _p(att)))
         return att
+
+    # ---- level crossings (include/geoac_levels.h): found on the device behind the per-ray sums of every epoch; nothing is computed here ----
+    def set_levels(self, z_km, cap=8):
+        """geoac_set_levels: up to 8 altitudes [km above sea level], strictly ascending, above z_grnd and below the vertical limit; every later launch then
+        keeps, per (ray, level), a count of the passages through the altitude and the first `cap` of them (1 .. 64).  An empty list leaves the mode."""
+        z = _arr(z_km).reshape(-1)
+        self._chk(self.lib.geoac_set_levels(self._h, len(z), _p(z) if len(z) else None, int(cap)))
+
+    @property
+    def levels(self):
+        """(z_km, cap) of the current level list (an empty array: none)"""
+        n, cap = ctypes.c_int(0), ctypes.c_int(0)
+        z = np.zeros(MAX_LEVELS)
+        self._chk(self.lib.geoac_get_levels(self._h, ctypes.byref(n), _p(z), ctypes.byref(cap)))
+        return z[:n.value].copy(), cap.value
+
+    def fetch_levels(self):
+        """crossings of the last launch: (count, rec) - count int32 [M][n_rays][L], it keeps running past cap; rec float64 [M][n_rays][L][cap][12] in the
+        LVL layout, the first `cap` crossings in path order, zero past the count.  M = n_sources * n_members, the axis dropped when M == 1 as fetch() drops it."""
+        z, cap = self.levels
+        shape = (self._launch_members(), self.n_rays, len(z))
+        count = np.zeros(shape, dtype=np.int32)
+        rec = np.zeros(shape + (cap, LVL_STRIDE))
+        self._chk(self.lib.geoac_fan_fetch_levels(self._h, _p(rec), count.ctypes.data_as(ctypes.c_void_p)))
+        if shape[0] == 1:
+            count, rec = count[0], rec[0]
+        return count, rec
+
+    def levels_dev(self):
+        """device buffers of the last launch's crossings: ((rec_ptr, rec_bytes), (count_ptr, count_bytes)), valid until the next launch or set_levels"""
+        rp, rb, cp, cb = ctypes.c_void_p(), ctypes.c_size_t(), ctypes.c_void_p(), ctypes.c_size_t()
+        self._chk(self.lib.geoac_fan_levels_dev(self._h, ctypes.byref(rp), ctypes.byref(rb), ctypes.byref(cp), ctypes.byref(cb)))
+        return (rp.value, rb.value), (cp.value, cb.value)
 
     # ---- arrival maps (include/geoac_map.h): the binning runs on the device; nothing is computed here ----
     def _launch_members(self):

@@ -25,6 +25,7 @@
 #include "geoac_stations_int.h"
 #include "geoac_tubemap_int.h"
 #include "geoac_refine_int.h"
+#include "geoac_levels_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
 extern "C" hipError_t geoac_launch_init(const GeoacDevParams* P, hipStream_t s);
@@ -234,6 +235,13 @@ struct geoac_ctx {
     std::vector<hipEvent_t> evf;                  // per epoch: the frequency post-pass has finished (k_accum_freq may start)
     int last_n_freq = 1;                          // of the last completed launch
     unsigned long long freq_fixup_segments = 0;   // last launch: (segment, frequency) pairs the extra frequencies' tables did not serve
+    // level crossings (geoac_set_levels, include/geoac_levels.h): none of the buffers below exists, and k_levels never runs, while n_levels == 0
+    int n_levels = 0, lvl_cap = GEOAC_LVL_DEF_CAP;
+    double levels[GEOAC_MAX_LEVELS] = {0, 0, 0, 0, 0, 0, 0, 0};     // z_km
+    DevBuf lvl_state, lvl_rec, lvl_count;         // [GEOAC_LVL_NSTATE][n_pad]; [M n_rays][L][cap][GEOAC_LVL_STRIDE]; [M n_rays][L]
+    unsigned long long lvl_version = 1, last_lvl_version = 0;       // bumped by geoac_set_levels; its value at the last completed launch with levels (0: none)
+    int last_n_levels = 0, last_lvl_cap = 0;      // of the last completed launch
+    long long last_lvl_rays = 0;                  // ... its M n_rays
     // arrival maps (geoac_map.hip): map_gen is bumped by everything that invalidates a map - a launch, new angles, an atmosphere upload, geoac_set_sources,
     // geoac_set_frequencies; launch_gen is its value when the last launch completed, so records, level table and maps are current while the two agree.
     // map_state belongs to geoac_map.hip and stays NULL (nothing allocated, nothing launched) until the first geoac_fan_map / geoac_fan_fetch_level
@@ -547,7 +555,8 @@ int geoac_destroy(geoac_ctx* ctx){
                        &ctx->ev_row[0], &ctx->ev_row[1], &ctx->ev_row[2], &ctx->ev_m[0], &ctx->ev_m[1], &ctx->ev_m[2],
                        &ctx->ev_amp[0], &ctx->ev_amp[1], &ctx->ev_amp[2], &ctx->nev[0], &ctx->nev[1], &ctx->nev[2], &ctx->smp_out,
                        &ctx->d_gx, &ctx->d_gy, &ctx->d_gz, &ctx->d_gtab, &ctx->d_gtab8, &ctx->d_consts, &ctx->sub_flags, &ctx->ncols, &ctx->atab, &ctx->ppfix,
-                       &ctx->fcontrib[0], &ctx->fcontrib[1], &ctx->fcontrib[2], &ctx->fstate, &ctx->fatten, &ctx->ffix, &ctx->fcnt };
+                       &ctx->fcontrib[0], &ctx->fcontrib[1], &ctx->fcontrib[2], &ctx->fstate, &ctx->fatten, &ctx->ffix, &ctx->fcnt,
+                       &ctx->lvl_state, &ctx->lvl_rec, &ctx->lvl_count };
     for(DevBuf* b : bufs) b->release();
     for(int b = 0; b < 6; b++){ ctx->nrows[b].release(); ctx->legend[b].release(); ctx->nlegend[b].release(); ctx->colmap[b].release(); }
     g_deferred.drain();
@@ -584,6 +593,7 @@ int geoac_clone(geoac_ctx* src, geoac_ctx** out){
     if(src->n_members > 1) return fail(src, GEOAC_E_UNSUPPORTED, std::string("clone: not available for an ensemble ") + ens_hint(src));
     if(src->n_src > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a source set is active (geoac_set_sources); set a single source first");
     if(src->n_freq > 1) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while a frequency set is active (geoac_set_frequencies); set a single frequency first");
+    if(src->n_levels > 0) return fail(src, GEOAC_E_UNSUPPORTED, "clone: not available while levels are set (geoac_set_levels); set 0 levels first");
     geoac_ctx* c = nullptr;
     int rc = geoac_create(&c, src->eqset, src->device);
     if(rc) return rc;
@@ -684,6 +694,7 @@ int geoac_refuse_ensemble(geoac_ctx* ctx, const char* what){
     if(!ctx) return GEOAC_OK;
     if(ctx->n_src > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a source set is active (geoac_set_sources); set a single source first");
     if(ctx->n_freq > 1) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while a frequency set is active (geoac_set_frequencies); set a single frequency first");
+    if(ctx->n_levels > 0) return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available while levels are set (geoac_set_levels); set 0 levels first");
     if(ctx->n_members <= 1) return GEOAC_OK;
     return fail(ctx, GEOAC_E_UNSUPPORTED, std::string(what) + ": not available for an ensemble " + ens_hint(ctx));
 }
@@ -747,6 +758,39 @@ int geoac_set_frequencies(geoac_ctx* ctx, int n_freq, const double* freq_hz){
 int geoac_get_frequencies(geoac_ctx* ctx, int* n_freq){
     if(!ctx || !n_freq) return fail(ctx, GEOAC_E_INVALID, "get_frequencies: bad arguments");
     *n_freq = ctx->n_freq;
+    return GEOAC_OK;
+}
+
+// the first thing wrong with the context's level list under its parameters now, as a status (GEOAC_OK: nothing); `what` names the caller in the message
+static int levels_status(geoac_ctx* ctx, const char* what, int n_levels, const double* z_km, int cap){
+    const char* fault = nullptr;
+    const int rc = geoac_levels_check(ctx->eqset, &ctx->prm, n_levels, z_km, cap, &fault);
+    return rc ? fail(ctx, rc, std::string(what) + ": " + (fault ? fault : "bad level list")) : GEOAC_OK;
+}
+
+int geoac_set_levels(geoac_ctx* ctx, int n_levels, const double* z_km, int cap){
+    if(!ctx) return GEOAC_E_INVALID;
+    if(int rc = levels_status(ctx, "set_levels", n_levels, z_km, cap)) return rc;
+    ctx->lvl_version++;
+    ctx->n_levels = n_levels;
+    ctx->lvl_cap = cap > 0 ? cap : GEOAC_LVL_DEF_CAP;
+    for(int l = 0; l < GEOAC_MAX_LEVELS; l++) ctx->levels[l] = l < n_levels ? z_km[l] : 0.0;
+    if(n_levels == 0){                                            // leaves the mode: nothing of it is held
+        ctx->last_lvl_version = 0; ctx->last_n_levels = 0;
+        if(ctx->lvl_state.p || ctx->lvl_rec.p || ctx->lvl_count.p){
+            HIPCHK(hipSetDevice(ctx->device));
+            if(ctx->stream) HIPCHK(hipStreamSynchronize(ctx->stream));
+            ctx->lvl_state.release(); ctx->lvl_rec.release(); ctx->lvl_count.release();
+        }
+    }
+    return GEOAC_OK;
+}
+
+int geoac_get_levels(geoac_ctx* ctx, int* n_levels, double* z_km, int* cap){
+    if(!ctx || !n_levels) return fail(ctx, GEOAC_E_INVALID, "get_levels: bad arguments");
+    *n_levels = ctx->n_levels;
+    if(z_km) for(int l = 0; l < ctx->n_levels; l++) z_km[l] = ctx->levels[l];
+    if(cap) *cap = ctx->lvl_cap;
     return GEOAC_OK;
 }
 
@@ -1039,6 +1083,10 @@ static int fan_launch_once(geoac_ctx* ctx){
     if(F > 1 && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
         return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available while a frequency set is active; set a single frequency first");
     if(F > 1 && is_grid) return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: frequency sets are available for the stratified equation sets only");
+    const int n_lev = ctx->n_levels;              // level crossings: k_levels behind the sums of every epoch
+    if(n_lev > 0 && (p.mode & (GEOAC_MODE_WRITE_RAYS | GEOAC_MODE_WRITE_CAUSTICS)))
+        return fail(ctx, GEOAC_E_UNSUPPORTED, "fan_launch: sample capture (WriteRays / WriteCaustics) is not available while levels are set (geoac_set_levels); set 0 levels first");
+    if(n_lev > 0) if(int rc = levels_status(ctx, "fan_launch: levels (geoac_set_levels) against the parameters now in force", n_lev, ctx->levels, ctx->lvl_cap)) return rc;
     GeoacDevParams P{};
     P.eqset = ctx->eqset; P.calc_amp = p.calc_amp ? 1 : 0; P.mode = p.mode; P.bounces = p.bounces;
     P.n_rays = ctx->n_rays * M; P.n_pad = ctx->n_pad;
@@ -1126,6 +1174,11 @@ static int fan_launch_once(geoac_ctx* ctx){
     //      Measured on the metric fan (GEOAC_S_ROWS sweep, hybrid build): 4096 rows 179 ms per pass, 8192 167, 12288 167, 16384 173 -
     //      every epoch boundary costs a launch + table reload, while very long epochs leave the last post-pass uncovered ----
     size_t row_bytes = (size_t)P.pathw * P.n_pad * sizeof(double);
+    // level crossings: [M n_rays][L][cap] records, [M n_rays][L] counts, the running sums of k_levels
+    const size_t lvl_rec_bytes = n_lev > 0 ? sizeof(double) * GEOAC_LVL_STRIDE * (size_t)P.n_rays * n_lev * ctx->lvl_cap : 0;
+    const size_t lvl_count_bytes = n_lev > 0 ? sizeof(int) * (size_t)P.n_rays * n_lev : 0;
+    const size_t lvl_state_bytes = n_lev > 0 ? sizeof(double) * GEOAC_LVL_NSTATE * (size_t)P.n_pad : 0;
+    const size_t lvl_need = lvl_rec_bytes + lvl_count_bytes + lvl_state_bytes;
     // (CHUNK_GIB: the cap per path chunk; a device that is shared - several ranks or contexts, torch tensors - can be given a smaller one than the 40 GiB that suit a GPU of its own)
     long long s_rows = (long long)(((unsigned long long)ctx->chunk_gib << 30) / row_bytes);      // round 2: 40 GiB per chunk (config 3: 2760 -> 6900 rows, 21 -> 9 epochs, +8 %); the free-memory clamp below still applies
     if(F > 1) s_rows = s_rows * (P.pathw + 2) / (P.pathw + 1 + F);      // (the frequency contributions inside the same budget: pathw + 2 doubles per row and column become pathw + 2 + F - 1)
@@ -1139,10 +1192,14 @@ static int fan_launch_once(geoac_ctx* ctx){
             size_t held = 0;
             for(int b = 0; b < 3; b++) held += ctx->path[b].bytes + ctx->contrib[b].bytes + ctx->fcontrib[b].bytes;
             const size_t per_row = (size_t)(ctx->two_chunks ? 2 : 3) * (row_bytes + (2 + (size_t)(F - 1)) * (size_t)P.n_pad * sizeof(double));
-            const double budget = 0.8 * (double)(free_b + held);
+            // (level crossings: records, counts and running sums do not scale with the epoch - what of them is still to be allocated comes off the budget)
+            const size_t lvl_held = ctx->lvl_rec.bytes + ctx->lvl_count.bytes + ctx->lvl_state.bytes;
+            const size_t lvl_new = lvl_need > lvl_held ? lvl_need - lvl_held : 0;
+            const double budget = 0.8 * (double)(free_b + held) - (double)lvl_new;
             if((double)per_row * (double)s_rows > budget){
                 long long fit = (long long)(budget / (double)per_row);
-                if(fit < 16) return fail(ctx, GEOAC_E_NOMEM, "fan_launch: not enough free device memory for the path chunks of this fan (" + std::to_string(free_b >> 20) + " MiB free)");
+                if(fit < 16) return fail(ctx, GEOAC_E_NOMEM, "fan_launch: not enough free device memory for the path chunks of this fan (" + std::to_string(free_b >> 20) + " MiB free" +
+                                         (n_lev > 0 ? ", " + std::to_string(lvl_need >> 20) + " MiB of level-crossing records, counts and sums wanted beside them" : std::string()) + ")");
                 s_rows = fit;
             }
         }
@@ -1359,8 +1416,9 @@ static int fan_launch_once(geoac_ctx* ctx){
     const int n_chunks = ctx->two_chunks ? 2 : 3;     // three path chunks in rotation: the post-pass may lag the RK4 by more than one epoch (measured: GeoAc3D 360 x 90 fan 212 -> 160 ms; GEOAC_TWO_CHUNKS=1 for A/B)
     // Chunk reuse follows the data (stratified sets, arrivals only, one frequency; see the epoch loop): k_rk4(e) waits for the post-pass of epoch e - n alone, and
     // the small per-epoch arrays, which k_accum(e - n) may still be reading then, rotate over 2 n sets of their own.  Sample capture (k_accum reads path rows and the
-    // event lists), frequency sets (fcontrib, k_accum_freq) and the grid sets keep one rotation of n for everything and the wait for k_accum(e - n).
-    const bool data_edges = !is_grid && !sampling && F == 1 && !ctx->no_overlap && ctx->reuse_edges;      // (REUSE_EDGES=0: the wait for k_accum for every fan, A/B)
+    // event lists), frequency sets (fcontrib, k_accum_freq), level crossings (k_levels reads path rows behind k_accum, on its stream) and the grid sets keep one
+    // rotation of n for everything and the wait for k_accum(e - n) - evs[4 (e - n) + 3], which is recorded behind k_accum_freq and k_levels where they run.
+    const bool data_edges = !is_grid && !sampling && F == 1 && n_lev == 0 && !ctx->no_overlap && ctx->reuse_edges;      // (REUSE_EDGES=0: the wait for k_accum for every fan, A/B)
     const int n_small = data_edges ? 2 * n_chunks : n_chunks;
     if(compact) for(int b = 0; b < n_small; b++) HIPCHK(ctx->colmap[b].ensure(sizeof(int) * ((size_t)P.n_pad + M)));      // (ensembles: + the members' range starts)
     for(int b = 0; b < n_small; b++){
@@ -1377,6 +1435,17 @@ static int fan_launch_once(geoac_ctx* ctx){
         }
     }
 
+    if(n_lev > 0){                                                // level crossings: before the chunks, which give way (below) when the device is short
+        hipError_t e = ctx->lvl_state.ensure(lvl_state_bytes);
+        if(e == hipSuccess) e = ctx->lvl_rec.ensure(lvl_rec_bytes);
+        if(e == hipSuccess) e = ctx->lvl_count.ensure(lvl_count_bytes);
+        if(e == hipErrorOutOfMemory){
+            (void)hipGetLastError();
+            return fail(ctx, GEOAC_E_NOMEM, "fan_launch: no device memory for the level-crossing records, counts and sums (" + std::to_string(lvl_need >> 20) + " MiB for " +
+                        std::to_string(P.n_rays) + " rays x " + std::to_string(n_lev) + " levels x " + std::to_string(ctx->lvl_cap) + " crossings)");
+        }
+        if(e != hipSuccess) return hipfail(ctx, e, "level-crossing buffers");
+    }
     // the path chunks themselves.  The free-memory figure above can be stale by the time they are allocated (another process on the same
     // device sized its own chunks from the same figure): on an out-of-memory answer give the chunks back, halve the epoch and try again.
     for(;;){
@@ -1446,6 +1515,16 @@ static int fan_launch_once(geoac_ctx* ctx){
         HIPCHK(hipMemsetAsync(ctx->fatten.p, 0, sizeof(double) * n_att, s));
         HIPCHK(hipMemsetAsync(ctx->fcnt.p, 0, 2 * sizeof(unsigned long long), s));
     }
+    // level crossings: the block of k_levels; its running sums, the records and the counts start from zero
+    GeoacLevelParams Lq{};
+    if(n_lev > 0){
+        Lq.n_levels = n_lev; Lq.cap = ctx->lvl_cap; Lq.hidx = is_sph ? 0 : 2;      // (EQ::HIDX of the four sets that come here)
+        for(int l = 0; l < n_lev; l++) Lq.lev[l] = is_sph ? p.r_earth + ctx->levels[l] : ctx->levels[l];      // (added once, here, as P.ground is)
+        Lq.state = (double*)ctx->lvl_state.p; Lq.rec = (double*)ctx->lvl_rec.p; Lq.count = (int*)ctx->lvl_count.p;
+        HIPCHK(hipMemsetAsync(ctx->lvl_state.p, 0, lvl_state_bytes, s));
+        HIPCHK(hipMemsetAsync(ctx->lvl_rec.p, 0, lvl_rec_bytes, s));
+        HIPCHK(hipMemsetAsync(ctx->lvl_count.p, 0, lvl_count_bytes, s));
+    }
     HIPCHK(hipMemsetAsync(ctx->counters.p, 0, 32 * sizeof(unsigned long long), s));
     HIPCHK(hipEventRecord(ctx->ev0, s));
     HIPCHK(geoac_launch_init(&P, s));
@@ -1505,6 +1584,9 @@ static int fan_launch_once(geoac_ctx* ctx){
             if(sa != sp) HIPCHK(hipStreamWaitEvent(sa, ctx->evf[e], 0));
             HIPCHK(geoac_launch_accum_freq(&Pq, &Qq, sa));
         }
+        // level crossings: k_levels reads path[e % n], contrib[e % n] and the small arrays of this epoch behind the sums, on their stream - evs[4e + 3] below, which
+        // frees all of them for epoch e + n (no data_edges with levels set), is recorded behind it
+        if(n_lev > 0) HIPCHK(geoac_launch_levels(&Pq, &Lq, sa));
         HIPCHK(hipEventRecord(ctx->evs[4 * e + 3], sa));
         return GEOAC_OK;
     };
@@ -1542,7 +1624,7 @@ static int fan_launch_once(geoac_ctx* ctx){
         //      k_postpass(e - n): the wait is for evp[e - n].  contrib[b] is written by k_postpass(e) alone, which waits for k_accum(e - n) itself (enqueue_post).
         //      The small arrays of set e % 2n were read last by k_accum(e - 2n): that has finished, because k_postpass(e - n) did not start before evs[4(e - 2n) + 3]
         //      and k_rk4(e) does not start before k_postpass(e - n) has ended - so 2 n sets suffice.
-        //      Otherwise (sample capture, frequency sets, grid sets, one stream): everything of epoch e - n, k_accum included. ----
+        //      Otherwise (sample capture, frequency sets, level crossings, grid sets, one stream): everything of epoch e - n, k_accum and what follows it on its stream included. ----
         if(e >= (size_t)n_chunks) HIPCHK(hipStreamWaitEvent(s, data_edges ? ctx->evp[e - n_chunks] : ctx->evs[4 * (e - n_chunks) + 3], 0));
         if(compact && e >= 1){
             // columns of this epoch = rays alive after the previous one; the launch is sized by the newest live count the host has
@@ -1637,6 +1719,8 @@ static int fan_launch_once(geoac_ctx* ctx){
         ctx->freq_fixup_segments = 0;
         if(F > 1) HIPCHK(hipMemcpy(&ctx->freq_fixup_segments, (const unsigned long long*)ctx->fcnt.p + 1, sizeof(fx), hipMemcpyDeviceToHost)); }
     ctx->last_n_freq = F;
+    ctx->last_n_levels = n_lev; ctx->last_lvl_cap = n_lev > 0 ? ctx->lvl_cap : 0; ctx->last_lvl_rays = n_lev > 0 ? (long long)P.n_rays : 0;
+    ctx->last_lvl_version = n_lev > 0 ? ctx->lvl_version : 0;
     if(ctx->trace_epochs && P.trio){
         unsigned long long v = 0;
         HIPCHK(hipMemcpy(&v, (const unsigned long long*)ctx->counters.p + 30, sizeof(v), hipMemcpyDeviceToHost));
@@ -1790,6 +1874,36 @@ int geoac_fan_fetch_atten(geoac_ctx* ctx, double* atten_host){
         return GEOAC_OK;
     }
     HIPCHK(hipMemcpyAsync(atten_host, ctx->fatten.p, sizeof(double) * n * (size_t)ctx->last_n_freq, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GEOAC_OK;
+}
+
+// level crossings of the last completed launch (include/geoac_levels.h)
+static int levels_current(geoac_ctx* ctx, const char* what){
+    if(!ctx) return GEOAC_E_INVALID;
+    if(!ctx->ran || ctx->last_lvl_version == 0)
+        return fail(ctx, GEOAC_E_INVALID, std::string(what) + ": the last completed launch had no levels set (geoac_set_levels, then geoac_fan_launch)");
+    if(ctx->last_lvl_version != ctx->lvl_version)
+        return fail(ctx, GEOAC_E_INVALID, std::string(what) + ": the level list has changed since the last completed launch (launch again)");
+    return GEOAC_OK;
+}
+
+int geoac_fan_levels_dev(geoac_ctx* ctx, void** rec_dev, size_t* rec_bytes, void** count_dev, size_t* count_bytes){
+    if(int rc = levels_current(ctx, "fan_levels_dev")) return rc;
+    const size_t n = (size_t)ctx->last_lvl_rays * ctx->last_n_levels;
+    if(rec_dev) *rec_dev = ctx->lvl_rec.p;
+    if(rec_bytes) *rec_bytes = sizeof(double) * GEOAC_LVL_STRIDE * n * ctx->last_lvl_cap;
+    if(count_dev) *count_dev = ctx->lvl_count.p;
+    if(count_bytes) *count_bytes = sizeof(int) * n;
+    return GEOAC_OK;
+}
+
+int geoac_fan_fetch_levels(geoac_ctx* ctx, double* rec_out, int32_t* count_out){
+    if(int rc = levels_current(ctx, "fan_fetch_levels")) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    const size_t n = (size_t)ctx->last_lvl_rays * ctx->last_n_levels;
+    if(rec_out) HIPCHK(hipMemcpyAsync(rec_out, ctx->lvl_rec.p, sizeof(double) * GEOAC_LVL_STRIDE * n * ctx->last_lvl_cap, hipMemcpyDeviceToHost, ctx->stream));
+    if(count_out) HIPCHK(hipMemcpyAsync(count_out, ctx->lvl_count.p, sizeof(int) * n, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return GEOAC_OK;
 }

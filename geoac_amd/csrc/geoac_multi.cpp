@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/geoac_multi.h"
+#include "../../include/geoac_levels.h"
 
 struct geoac_pool {
     int eqset = 0;
@@ -77,6 +78,7 @@ int geoac_pool_fan_run(geoac_pool* p, int n_rays, const double* theta, const dou
     for(geoac_ctx* c : p->ctx){ int k = 1; if(geoac_get_members(c, &k) == GEOAC_OK && k > 1) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: ensembles are not available in the pool"); }
     for(geoac_ctx* c : p->ctx){ int k = 1; if(geoac_get_sources(c, &k) == GEOAC_OK && k > 1) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: a source set (geoac_set_sources) is not available in the pool"); }
     for(geoac_ctx* c : p->ctx){ int k = 1; if(geoac_get_frequencies(c, &k) == GEOAC_OK && k > 1) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: a frequency set (geoac_set_frequencies) is not available in the pool"); }
+    for(geoac_ctx* c : p->ctx){ int k = 0; if(geoac_get_levels(c, &k, nullptr, nullptr) == GEOAC_OK && k > 0) return pool_fail(p, GEOAC_E_UNSUPPORTED, "pool_fan_run: levels (geoac_set_levels) are not available in the pool"); }
     // the record stride comes from the contexts themselves (their defaults or whatever was set through the pool or through
     // geoac_pool_ctx): every context must write the same number of legs per ray in the same mode, or the groups would overlap
     geoac_params p0{};
