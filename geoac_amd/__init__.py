@@ -13,4 +13,5 @@ from .api import (  # noqa: F401
     RefineSpec, refine_spec, refine_check, RFN, RFN_STRIDE, RFN_STATUS, RFN_MAX_RAY_MEMBERS,
     TubeSpec, tube_spec, tube_check, TUBE, TUBE_MAX_SPAN, TUBE_COOP_MIN,
     levels_check, LVL, LVL_STRIDE, MAX_LEVELS,
+    LStationSpec, lstation_spec, lstation_check, LSTA, LSTA_STRIDE,
 )

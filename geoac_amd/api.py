@@ -97,6 +97,37 @@ def station_check(eqset, spec, n_rays, n_sta):
         raise GeoAcError(f"geoac_station_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
 
 
+class LStationSpec(ctypes.Structure):
+    """geoac_lstation_spec (include/geoac_lstations.h): lattice of the launch angles, legs and ordinals that take part, edge filter and list length
+    of a level-station search"""
+    _fields_ = [("n_theta", ctypes.c_int), ("n_phi", ctypes.c_int), ("phi_periodic", ctypes.c_int), ("leg_min", ctypes.c_int), ("leg_max", ctypes.c_int),
+                ("ord_max", ctypes.c_int), ("edge_max", ctypes.c_double), ("cap", ctypes.c_int)]
+
+
+LSTA_STRIDE = 16
+LSTA = dict(LEG=0, DIR=1, ORD=2, TRI=3, RAY0=4, ORIENT=5, W0=6, W1=7, W2=8, THETA=9, PHI=10, TTIME=11, ATTEN=12, N0=13)
+
+
+def lstation_spec(n_theta, n_phi, phi_periodic=False, leg_min=0, leg_max=2**31 - 1, ord_max=1, edge_max=np.inf, cap=16):
+    """an LStationSpec from plain values"""
+    return LStationSpec(int(n_theta), int(n_phi), 1 if phi_periodic else 0, int(leg_min), int(leg_max), int(ord_max), float(edge_max), int(cap))
+
+
+def _level_of(level_of):
+    return np.ascontiguousarray(level_of, dtype=np.int32).reshape(-1)
+
+
+def lstation_check(eqset, spec, n_rays, n_levels, level_of):
+    """geoac_lstation_check: host-only validation (no GPU needed) of a spec and the stations' level indices; raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_lstation_fault.restype = ctypes.c_char_p
+    lv = _level_of(level_of)
+    args = (int(eqset), ctypes.byref(spec), int(n_rays), int(n_levels), len(lv), lv.ctypes.data_as(ctypes.c_void_p))
+    rc = lib.geoac_lstation_check(*args)
+    if rc:
+        raise GeoAcError(f"geoac_lstation_check: {lib.geoac_strerror(rc).decode()}: {lib.geoac_lstation_fault(*args).decode()}")
+
+
 class RefineSpec(ctypes.Structure):
     """geoac_refine_spec (include/geoac_refine.h): round limit, shrink limit, tolerance [km] and step cut [deg] of a station refinement"""
     _fields_ = [("max_iter", ctypes.c_int), ("max_shrink", ctypes.c_int), ("tol", ctypes.c_double), ("step_max_deg", ctypes.c_double)]
@@ -611,6 +642,34 @@ class FanContext:
         """HIP-event time of the last stations() on the context's stream [ms]"""
         ms = ctypes.c_double(0)
         self._chk(self.lib.geoac_fan_stations_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    # ---- level stations (include/geoac_lstations.h): branch table, search and interpolation run on the device; nothing is computed here ----
+    def level_stations(self, spec=None, sta=None, level_of=None, **kw):
+        """geoac_fan_level_stations of the last launch (one with set_levels): `spec` an LStationSpec, or the arguments of lstation_spec(); sta [n_sta][2]
+        in the map's axes (lat, lon [deg] / x, y [km]); level_of [n_sta] indices into the launch's level list.  Returns hits [M][n_sta] u32 (the true
+        count, may exceed cap) and rows [M][n_sta][cap][LSTA_STRIDE] (columns LSTA).  May be called again with another spec or other stations
+        without a new launch."""
+        if spec is None:
+            spec = lstation_spec(**kw)
+        sta = _arr(sta)
+        if sta.ndim != 2 or sta.shape[1] != 2:
+            raise GeoAcError(f"level_stations: sta must have shape [n_sta][2] (got {sta.shape})")
+        lv = _level_of(level_of)
+        if len(lv) != len(sta):
+            raise GeoAcError(f"level_stations: level_of must hold one level index per station (got {len(lv)} for {len(sta)} stations)")
+        self._chk(self.lib.geoac_fan_level_stations(self._h, ctypes.byref(spec), len(sta), _p(sta), lv.ctypes.data_as(ctypes.c_void_p)))
+        M, R, cap = (ctypes.c_int(0) for _ in range(3))
+        self._chk(self.lib.geoac_fan_level_stations_shape(self._h, *[ctypes.byref(v) for v in (M, R, cap)]))
+        M, R, cap = M.value, R.value, cap.value
+        hits, rows = np.empty((M, R), dtype=np.uint32), np.empty((M, R, cap, LSTA_STRIDE))
+        self._chk(self.lib.geoac_fan_level_stations_fetch(self._h, hits.ctypes.data_as(ctypes.c_void_p), _p(rows)))
+        return hits, rows
+
+    def level_stations_timing(self):
+        """HIP-event time of the last level_stations() on the context's stream [ms]"""
+        ms = ctypes.c_double(0)
+        self._chk(self.lib.geoac_fan_level_stations_timing(self._h, ctypes.byref(ms)))
         return ms.value
 
     # ---- station refinement (include/geoac_refine.h): rounds, step rule and rows run on the device; nothing is computed here ----

@@ -25,6 +25,7 @@
 #include "geoac_stations_int.h"
 #include "geoac_tubemap_int.h"
 #include "geoac_refine_int.h"
+#include "geoac_lstations_int.h"
 #include "geoac_levels_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
@@ -250,6 +251,7 @@ struct geoac_ctx {
     void* sta_state = nullptr;                    // station arrivals (geoac_stations.hip): NULL until the first geoac_fan_stations
     void* tube_state = nullptr;                   // tube maps (geoac_tubemap.hip): NULL until the first geoac_fan_tubemap
     void* rfn_state = nullptr;                    // station refinement (geoac_refine.hip): NULL until the first geoac_fan_refine
+    void* lsta_state = nullptr;                   // level stations (geoac_lstations.hip): NULL until the first geoac_fan_level_stations
     std::vector<double> rfn_mem;                  // [M][GEOAC_RFN_MEMW] of the last geoac_rfn_view
     std::vector<double> ens_u, ens_v;             // every member's winds on the host (K > 1), beside ens_T: the Mach numbers at the source the refinement needs
     std::string err;
@@ -549,6 +551,7 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->map_state){ geoac_map_release(ctx->map_state); ctx->map_state = nullptr; }
     if(ctx->sta_state){ geoac_sta_release(ctx->sta_state); ctx->sta_state = nullptr; }
     if(ctx->tube_state){ geoac_tube_release(ctx->tube_state); ctx->tube_state = nullptr; }
+    if(ctx->lsta_state){ geoac_lsta_release(ctx->lsta_state); ctx->lsta_state = nullptr; }
     if(ctx->rfn_state){ geoac_rfn_release(ctx->rfn_state); ctx->rfn_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
@@ -1927,7 +1930,7 @@ int geoac_launch_view(geoac_ctx* ctx, int slot, GeoacLaunchView* v){
     int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
     if(rc) return rc;
     v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
-    v->state = slot == GEOAC_SLOT_STA ? &ctx->sta_state : (slot == GEOAC_SLOT_TUBE ? &ctx->tube_state : &ctx->map_state);
+    v->state = slot == GEOAC_SLOT_STA ? &ctx->sta_state : (slot == GEOAC_SLOT_TUBE ? &ctx->tube_state : (slot == GEOAC_SLOT_LSTA ? &ctx->lsta_state : &ctx->map_state));
     return GEOAC_OK;
 }
 
