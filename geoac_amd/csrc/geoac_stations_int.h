@@ -1,6 +1,7 @@
 // geoac_stations_int.h - the seam between geoac_api.cpp (which owns geoac_ctx) and geoac_stations.hip (station arrivals,
 // include/geoac_stations.h), and what geoac_stations.hip owns for the other post-launch files: the landing table of a launch, the proof that
-// the launch angles are a lattice, and the stations of the current lists.
+// the launch angles are a lattice, and the stations of the current lists.  (The list walk itself, which geoac_lstations.hip runs too, is
+// geoac_lattice_list.h.)
 #ifndef GEOAC_STATIONS_INT_H_
 #define GEOAC_STATIONS_INT_H_
 

@@ -1,7 +1,7 @@
 // geoac_tri_rule.h - the station rule of include/geoac_stations.h, which is normative for this arithmetic: whether a point lies in a landing
-// triangle, and the weights of the corners.  Used by geoac_stations.hip (a station), geoac_tubemap.hip (a cell centre) and geoac_refine.hip
-// (the longitude difference).  Restated in tests/station_reference.py: every product is rounded before it is added, so contraction is off
-// from here on in whatever file includes this.
+// triangle, and the weights of the corners.  Used by geoac_lattice_list.h (a station, on the ground for geoac_stations.hip and at a level for
+// geoac_lstations.hip), geoac_tubemap.hip (a cell centre) and geoac_refine.hip (the longitude difference).  Restated in
+// tests/station_reference.py: every product is rounded before it is added, so contraction is off from here on in whatever file includes this.
 #ifndef GEOAC_TRI_RULE_H_
 #define GEOAC_TRI_RULE_H_
 

@@ -119,6 +119,42 @@ def test_overflow_keeps_the_first_rows(G):
     ctx.close()
 
 
+def test_two_chunks_and_the_periodic_seam(G):
+    """the case level stations have (tests/test_gpu_lstations.py), on the ground lists that run the same walk: GEOAC_EQ_GLOBAL, ToyAtmo, source (0, 30, 0), one
+    bounce, 30 inclinations x 72 azimuths over the whole circle: 29 x 72 = 2 088 cells, one full chunk of 2 048 and a tail of 40 (a partial trip).  Every
+    station is a convex blend of the four leg-0 landing points of one lattice cell (from the fetched records), so it lies inside the cell's image where that
+    is convex; four cells are in the seam column 71 -> 0, which is also the second chunk.  With tests/station_reference.py on the plain-C oracle's records of
+    this fan every corner of the 16 cells is VALID on leg 0 and every station has a row of its own cell: the own-cell assertion is dropped for 0 of 16"""
+    eq = H.EQ_GLOBAL
+    th, ph, nt, nph = SC.lattice(theta_min=10.0, theta_max=39.0, theta_step=1.0, phi_min=-180.0, phi_max=175.0, phi_step=5.0)
+    assert (nt, nph) == (30, 72)
+    ctx = _phys_ctx(G)
+    rec = ctx.run(th, ph)[0][None]
+    sp = SR.spec(nt, nph, phi_periodic=True, cap=6)
+    tri = SR.triangles(sp)
+    c0, c1 = (c[0, :, 0] for c in SR.landing(eq, rec))
+    cells = [(i, 71) for i in (2, 9, 17, 26)] + [(i, j) for i, j in zip((0, 5, 11, 14, 19, 23, 28, 7, 13, 21, 4, 16), (0, 6, 13, 21, 29, 36, 44, 52, 59, 66, 70, 33))]
+    sta = []
+    for i, j in cells:
+        a, b, c = tri[2 * (j * (nt - 1) + i)]
+        d = tri[2 * (j * (nt - 1) + i) + 1][2]
+        assert (rec[0, [a, b, c, d], 0, SR.REC["VALID"]] != 0).all(), (i, j)           # (an unsuitable fan fails here, loudly)
+        w = np.array([0.35, 0.3, 0.25, 0.1])                                       # (off the diagonal a - c: inside triangle (a, b, c) of a near-parallelogram)
+        lon = c1[[a, b, c, d]]
+        lon = lon[0] + SR._wrap180(lon - lon[0])
+        sta.append([float(w @ c0[[a, b, c, d]]), float(w @ lon)])
+    hits, rows, _ = _stations_and_reference(ctx, eq, rec, th, ph, np.array(sta), **sp)
+    kept = rows[0][rows[0][..., S["W0"]] != 0]
+    print(f"2 088 cells: hits {hits[0].tolist()}, triangles {sorted(set(kept[:, S['TRI']].astype(int)))}")
+    assert (hits[0] >= 1).all()
+    own = [any(int(t) // 2 == j * (nt - 1) + i for t in rows[0, k, :min(int(hits[0, k]), 6), S["TRI"]]) for k, (i, j) in enumerate(cells)]
+    assert all(own), own
+    assert (kept[:, S["TRI"]] >= 2 * 71 * (nt - 1)).any() and (kept[:, S["TRI"]] >= 2 * 2048).any()          # the seam column; the second chunk
+    seam = rows[0, :4, 0]
+    assert ((seam[:, S["PHI"]] > 175.0) & (seam[:, S["PHI"]] < 180.0)).all()            # continuous with corner 0 (175), not an average of 175 and -180
+    ctx.close()
+
+
 def test_repeatable_and_contention(G):
     case = MC.CASES["ensemble3-global"]
     ctx, rec, th, ph, nt, nph = _launch(G, case, None)
