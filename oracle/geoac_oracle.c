@@ -1264,6 +1264,32 @@ int orc_trace_leg0(orc_ctx* c, const ref_fan_cfg* cfg, double theta_deg, double 
     for(int m = 0; m < k; m++) memset(ROW(c, m), 0, sizeof(double) * (size_t)c->EqCnt);
     return chk ? -k : k;
 }
+/* ref_trace_path (oracle/ref_shim.h): every leg's rows 0 .. k with the running sums beside them, segment m - 1 added at row m = 1 .. k inclusive */
+int orc_trace_path(orc_ctx* c, const ref_fan_cfg* cfg, double theta_deg, double phi_deg, int64_t max_rows, double* rows, double* sums, int* leg_k, int* E){
+    if(c->eqset == GEOAC_EQ_2D) return -1;
+    apply_cfg(c, cfg);
+    set_launch(c, theta_deg, phi_deg);
+    set_ic(c, cfg);
+    *E = c->EqCnt;
+    double travel_time_sum = 0.0, attenuation = 0.0;
+    int64_t at = 0;
+    int legs = 0, k = 0, chk = 0;
+    for(int bnc_cnt = 0; bnc_cnt <= cfg->bounces; bnc_cnt++){
+        k = propagate_rk4(c, &chk);
+        if(at + k + 1 > max_rows){ legs = -1; break; }
+        for(int m = 0; m <= k; m++){
+            if(m >= 1){ travel_time_sum += tt_seg(c, m-1); attenuation += att_seg(c, m-1, cfg->freq); }
+            memcpy(rows + (size_t)(at + m) * c->EqCnt, ROW(c, m), sizeof(double) * (size_t)c->EqCnt);
+            sums[2*(at + m)] = travel_time_sum; sums[2*(at + m) + 1] = attenuation;
+        }
+        at += k + 1;
+        leg_k[legs++] = chk ? -k : k;
+        if(chk) break;
+        reflect(c, k);
+    }
+    for(int m = 0; m < k; m++) memset(ROW(c, m), 0, sizeof(double) * (size_t)c->EqCnt);
+    return legs;
+}
 
 /* ------------------------------------------------------------------------------------------ */
 /* range-dependent API                                                                          */

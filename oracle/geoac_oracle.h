@@ -39,6 +39,9 @@ void     orc_absorption_probe(orc_ctx*, int n, const double* x, const double* f,
 int      orc_tables(orc_ctx*, int cap, double* x, double* T, double* u, double* v, double* rho,
                     double* sT, double* su, double* sv, double* srho);
 int      orc_trace_leg0(orc_ctx*, const ref_fan_cfg* cfg, double theta_deg, double phi_deg, int max_rows, double* out, int* E);
+/* the plain-C twin of ref_trace_path (oracle/ref_shim.h): every leg's rows with the running travel time and attenuation beside each row */
+int      orc_trace_path(orc_ctx*, const ref_fan_cfg* cfg, double theta_deg, double phi_deg, int64_t max_rows, double* rows, double* sums,
+                        int* leg_k, int* E);
 
 /* range-dependent Cartesian set (GEOAC_EQ_3D_RNGDEP): grid of profiles <prefix><n>.met, n = ix*ny + iy */
 int      orc_load_grid(orc_ctx*, const char* prefix, const char* locx, const char* locy, const char* format, double z_grnd_at_load);

@@ -58,6 +58,12 @@ int     ref_load_grid(const char* prefix, const char* locx, const char* locy, co
 void    ref_grid_probe(int n, const double* x, const double* y, const double* z, double* out30, double* api8);
 /* full state row dump of one leg-0 propagation (for stepper-level tests): out rows*(E) doubles, returns k */
 int     ref_trace_leg0(const ref_fan_cfg* cfg, double theta_deg, double phi_deg, int max_rows, double* out, int* E);
+/* every leg of one ray, by the bounce loop ref_fan runs (bnc_cnt = 0 .. cfg->bounces): rows receives the legs one after another, leg j's
+ * rows 0 .. k_j (k_j + 1 rows of *E doubles); sums receives two doubles beside each row, the travel time and the attenuation accumulated up to
+ * that row - one TravelTimeSegment / SB_AttenSegment call per row m = 1 .. k_j INCLUSIVE, carried over the legs (the arrivals-only form of quirk
+ * Q7, not the WriteRays loop's m < k); leg_k[j] = k_j, negated where the leg ended by the break check (the last leg then).
+ * returns the number of legs run, or -1 where the rows would not fit max_rows (or the set has no such entry: the 2-D shim) */
+int     ref_trace_path(const ref_fan_cfg* cfg, double theta_deg, double phi_deg, int64_t max_rows, double* rows, double* sums, int* leg_k, int* E);
 
 #ifdef __cplusplus
 }

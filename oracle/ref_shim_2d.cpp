@@ -182,3 +182,5 @@ extern "C" int ref_trace_leg0(const ref_fan_cfg* cfg, double theta_deg, double p
     GeoAc_ClearSolutionArray(g_solution, k);
     return BreakCheck ? -k : k;
 }
+
+extern "C" int ref_trace_path(const ref_fan_cfg*, double, double, int64_t, double*, double*, int*, int*){ return -1; }

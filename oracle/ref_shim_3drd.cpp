@@ -191,3 +191,34 @@ extern "C" int ref_trace_leg0(const ref_fan_cfg* cfg, double theta_deg, double p
     GeoAc_ClearSolutionArray(g_solution, k);
     return BreakCheck ? -k : k;
 }
+
+extern "C" int ref_trace_path(const ref_fan_cfg* cfg, double theta_deg, double phi_deg, int64_t max_rows, double* rows, double* sums, int* leg_k, int* E){
+    apply_cfg(cfg);
+    double** solution = g_solution;
+    double z_src = std::max(z_grnd, cfg->src[2]);
+    GeoAc_theta = theta_deg*Pi/180.0;
+    GeoAc_phi = Pi/2.0 - phi_deg*Pi/180.0;
+    GeoAc_SetInitialConditions(solution, cfg->src[0], cfg->src[1], z_src);
+    *E = GeoAc_EqCnt;
+    double travel_time_sum = 0.0, attenuation = 0.0;
+    int64_t at = 0;
+    int legs = 0, k = 0; bool BreakCheck;
+    for(int bnc_cnt = 0; bnc_cnt <= cfg->bounces; bnc_cnt++){      /* the bounce loop of ref_fan */
+        k = GeoAc_Propagate_RK4(solution, BreakCheck);
+        if(at + k + 1 > max_rows){ legs = -1; break; }
+        for(int m = 0; m <= k; m++){
+            if(m >= 1){                                             /* m = 1 .. k inclusive: segments 0 .. k - 1, what GeoAc_TravelTime(solution, k) sums */
+                GeoAc_TravelTimeSegment(travel_time_sum, solution, m-1, m);
+                GeoAc_SB_AttenSegment(attenuation, solution, m-1, m, cfg->freq);
+            }
+            for(int e = 0; e < GeoAc_EqCnt; e++) rows[(size_t)(at + m)*GeoAc_EqCnt + e] = solution[m][e];
+            sums[2*(at + m)] = travel_time_sum; sums[2*(at + m) + 1] = attenuation;
+        }
+        at += k + 1;
+        leg_k[legs++] = BreakCheck ? -k : k;
+        if(BreakCheck) break;
+        GeoAc_SetReflectionConditions(solution,k);
+    }
+    GeoAc_ClearSolutionArray(solution,k);
+    return legs;
+}

@@ -80,6 +80,20 @@ class _FanLib:
                    _p(smp) if smp_cap else None, ctypes.c_int64(smp_cap), ctypes.byref(nsmp))
         return int(steps), rec, smp[:min(nsmp.value, smp_cap)], nsmp.value
 
+    def _trace_path(self, fn, pre, cfg, theta, phi, max_rows):
+        """every leg of one ray (oracle/ref_shim.h, ref_trace_path): a list of (k, rows [k + 1][E], sums [k + 1][2]), k < 0 where the leg ended
+        by the break check; sums = the travel time and attenuation accumulated up to each row, carried over the legs"""
+        rows = np.zeros(max_rows * 18); sums = np.zeros(max_rows * 2)
+        leg_k = (ctypes.c_int * (cfg.bounces + 1))(); E = ctypes.c_int(0)
+        n = fn(*pre, ctypes.byref(cfg), ctypes.c_double(theta), ctypes.c_double(phi), ctypes.c_int64(max_rows), _p(rows), _p(sums), leg_k, ctypes.byref(E))
+        assert n >= 1, f"trace_path -> {n}"
+        e, at, legs = E.value, 0, []
+        for j in range(n):
+            m = abs(leg_k[j]) + 1
+            legs.append((leg_k[j], rows[at * e:(at + m) * e].reshape(m, e).copy(), sums[at * 2:(at + m) * 2].reshape(m, 2).copy()))
+            at += m
+        return legs
+
 
 class Oracle(_FanLib):
     def __init__(self, eqset, met=TOYATMO, fmt="zTuvdp"):
@@ -89,7 +103,7 @@ class Oracle(_FanLib):
         L.orc_create.argtypes = [ctypes.c_int]
         L.orc_fan.restype = ctypes.c_int64
         for f in (L.orc_destroy, L.orc_load, L.orc_load_arrays, L.orc_fan, L.orc_atmo_probe,
-                  L.orc_absorption_probe, L.orc_tables, L.orc_trace_leg0, L.orc_limits, L.orc_load_grid, L.orc_grid_probe):
+                  L.orc_absorption_probe, L.orc_tables, L.orc_trace_leg0, L.orc_trace_path, L.orc_limits, L.orc_load_grid, L.orc_grid_probe):
             f.argtypes = None
         self.eqset = eqset
         self.ctx = ctypes.c_void_p(L.orc_create(eqset))
@@ -152,6 +166,9 @@ class Oracle(_FanLib):
                                     max_rows, _p(out), ctypes.byref(E))
         e = E.value; rows = min(abs(k) + 1, max_rows)
         return k, out[:rows * e].reshape(rows, e).copy()
+
+    def trace_path(self, cfg, theta, phi, max_rows=120000):
+        return self._trace_path(self.lib.orc_trace_path, (self.ctx,), cfg, float(theta), float(phi), max_rows)
 
     def __del__(self):
         try:
@@ -221,3 +238,6 @@ class RefShim(_FanLib):
                                     max_rows, _p(out), ctypes.byref(E))
         e = E.value; rows = min(abs(k) + 1, max_rows)
         return k, out[:rows * e].reshape(rows, e).copy()
+
+    def trace_path(self, cfg, theta, phi, max_rows=120000):
+        return self._trace_path(self.lib.ref_trace_path, (), cfg, float(theta), float(phi), max_rows)

@@ -1,5 +1,7 @@
-"""Level crossings on the GPU (include/geoac_levels.h, k_levels): against the compiled reference's own rows (tests/golden/levels_small.npz), against a closed
-form, against the records of the same launch on every equation set, bit for bit across launch plans and members, and the refusals.
+"""Level crossings on the GPU (include/geoac_levels.h, k_levels): against the compiled reference's own rows (tests/golden/levels_small.npz), against the
+reference's crossings, times and attenuations on every leg of all four sets (tests/golden/levels_legs.npz), against the path of the same launch as sample
+capture at stride 1 returns it (every instantiation, rows exactly on a level, elevated sources, chunk seams), against a closed form, against the records
+of the same launch on every equation set, bit for bit across launch plans and members, and the refusals.
 
 Fans are small: the fixture's six inclinations at azimuth -90 (plus azimuth 37 where noted), one bounce, range limit 300 km.  Every context of a given
 (set, fan, plan) is run once and shared, read-only."""
@@ -118,6 +120,214 @@ def test_leg0_crossings_match_the_reference_rows(G, fixture, eq):
             assert (mine[:, LT] >= lo).all() and (mine[:, LT] <= hi).all(), (r, l, mine[:, LT], lo, hi)
     print(f"{name}: {n} leg-0 crossings, largest position error against the reference's rows {worst:.3e}")
     assert n == fixture[f"{name}_count"].sum() and worst <= 1e-6
+
+
+# ---------------------------------------------------------------- every leg, four sets, times and attenuation (tests/golden/levels_legs.npz)
+@pytest.fixture(scope="module")
+def legs_fixture():
+    return np.load(LR.LEGS_FIXTURE)
+
+
+def _open(G, eq, tmp_path):
+    """a context with the set's atmosphere: ToyAtmo, or the ragged 7 x 4 grid"""
+    ctx = G.FanContext(eq, device=0)
+    if eq in (H.EQ_3D, H.EQ_GLOBAL):
+        ctx.load_met(H.TOYATMO)
+    else:
+        glob = eq == H.EQ_GLOBAL_RNGDEP
+        ctx.load_grid(*RD.write_grid_ragged(str(tmp_path), glob, short_paths=False), z_grnd=RD.ragged_load_z_grnd(glob))
+    return ctx
+
+
+def _legs_fan(eq, g):
+    """rays and parameters of a set of the legs fixture: two bounces"""
+    name = H.EQ_NAMES[eq]
+    if eq in (H.EQ_3D, H.EQ_GLOBAL):
+        params = dict(bounces=2, calc_amp=1, range_limit=float(g[f"{name}_range_limit"]))
+    else:
+        params = dict(bounces=2, calc_amp=1, src=tuple(g[f"{name}_src"]), z_grnd=float(g[f"{name}_z_grnd"]))
+    return g[f"{name}_theta"], g[f"{name}_phi"], params
+
+
+@pytest.mark.parametrize("eq", ALL_SETS)
+def test_all_legs_match_the_reference(G, legs_fixture, eq, tmp_path):
+    """LR.compare_with_fixture: counts per (ray, level, leg), LEG and DIR exact; FRAC, the interpolated row in all its components, TTIME and ATTEN within 1e-6
+    relative of what the compiled reference's rows and running sums give (tests/test_levels_host.py: the same call refuses five wrong kernels).  Worst
+    errors measured on an MI355X: DESIGN 8l."""
+    name = H.EQ_NAMES[eq]
+    th, ph, params = _legs_fan(eq, legs_fixture)
+    ctx = _open(G, eq, tmp_path)
+    ctx.set_params(mode=0, **params)
+    ctx.set_levels(legs_fixture[f"{name}_levels"], cap=int(legs_fixture[f"{name}_cap_needed"]))
+    ctx.run(th, ph)
+    count, lrec = ctx.fetch_levels()
+    ctx.close()
+    LR.compare_with_fixture(eq, count, lrec, legs_fixture)
+
+
+# ---------------------------------------------------------------- against the same launch's path (sample capture at stride 1)
+U = 2.0 ** -53
+
+
+def _pair(G, eq, tmp_path, th, ph, levels, cap=8, opts=None, **params):
+    """the fan twice under the same options: with levels, and with sample capture at stride 1 in their place (k_rk4<SMP> and k_accum's sample-capture branch:
+    code k_levels shares nothing with).  GEOAC_ABS_TABLE=0 in both: the exact post-pass writes every segment's contribution, so that both contexts sum the
+    same numbers whatever a table build decides.  Preconditions asserted here: the same step counts, every record column but TTIME / ATTEN the same bits;
+    a launch whose sample or event list overflowed raises; LR.rows_from_samples asserts rows 1 .. k - 1 of every leg, once each.
+    -> (records, count, crossing records, paths, rows per ray)"""
+    with G.options(**dict(opts or {}, GEOAC_ABS_TABLE="0")):
+        a = _open(G, eq, tmp_path)
+        a.set_params(mode=0, **params)
+        a.set_levels(levels, cap=cap)
+        rec, steps = a.run(th, ph)
+        count, lrec = a.fetch_levels()
+        src, geo = tuple(a.params.src), dict(z_grnd=a.params.z_grnd, r_earth=a.params.r_earth)
+        a.close()
+        b = _open(G, eq, tmp_path)
+        b.set_params(mode=G.api.MODE_WRITE_RAYS, sample_stride=1, **params)
+        rec_s, steps_s = b.run(th, ph)
+        smp = b.fetch_samples()
+        b.close()
+    assert steps == steps_s and (eq not in LR.SPHERICAL or geo["r_earth"] == LR.R_EARTH)
+    other = [c for c in range(H.REC_STRIDE) if c not in (TTIME, H.REC["ATTEN"])]
+    assert np.array_equal(np.ascontiguousarray(rec[..., other]).view(np.uint64), np.ascontiguousarray(rec_s[..., other]).view(np.uint64))
+    paths, n_rows = LR.rows_from_samples(eq, smp, rec_s, src, geo, rec)
+    assert n_rows.sum() == steps + int((rec[..., H.REC["STEPS"]] > 0).sum())
+    return rec, count, lrec, paths, n_rows
+
+
+def _check_against_path(eq, rec, count, lrec, paths, n_rows, levels, what):
+    """count, LEG, DIR and FRAC: the same bits as LR.restate_k_levels on the sampled path.  Cartesian sets: P0 .. P2 too (the sample rows hold x, y and
+    max(z, 0) unconverted, and no interior row lies below z = 0).  Spherical sets: the sample holds r - r_earth, exact for r_earth = 6370 and r < 8192 km
+    (both multiples of 2^-40, the difference needs fewer bits), and r_earth + that is r again - so the heights, FRAC and P0 are the same bits here as well,
+    with no room needed around a level; latitude and longitude come back from degrees through x 180, / pi, x pi, / 180, four roundings of 2^-53 relative each
+    on either row, and the interpolation's three operations round once each on either side: |got - want| <= 10 x 2^-53 (|want| + 1e-3), 1e-3 rad being more
+    than a step spans.  TTIME / ATTEN: both sides add the same contributions (_pair), grouped differently: within 4 n 2^-53 of the ray's final sum, n the
+    ray's rows."""
+    hi, cap = LR.hidx(eq), lrec.shape[2]
+    assert count.max() <= cap, (what, "raise cap")
+    lowest = LR.level_values(eq, levels)[0]
+    for legs in paths:
+        for j, (_, rows, _) in enumerate(legs):
+            assert j == 0 or rows[1, hi] < lowest, (what, "a crossing in the first segment behind a bounce: LR.rows_from_samples does not re-do that row")
+    wc, wl = LR.restate_fan(eq, paths, levels, cap)
+    assert np.array_equal(count, wc), (what, "counts", np.argwhere(count != wc)[:4])
+    exact = [LEG, DIR, FRAC, P0] if eq in LR.SPHERICAL else [LEG, DIR, FRAC, P0, P0 + 1, P0 + 2]
+    for c in exact:
+        assert np.array_equal(lrec[..., c].view(np.uint64), wl[..., c].view(np.uint64)), (what, "column", c, np.argwhere(lrec[..., c] != wl[..., c])[:4])
+    worst = {}
+    if eq in LR.SPHERICAL:
+        e = np.abs(lrec[..., P0 + 1:P0 + 3] - wl[..., P0 + 1:P0 + 3]) / (np.abs(wl[..., P0 + 1:P0 + 3]) + 1e-3)
+        worst["lat, lon / (10 x 2^-53)"] = float(e.max() / (10.0 * U))
+    final = np.array([[rec[r, len(legs) - 1, c] for c in (TTIME, H.REC["ATTEN"])] for r, legs in enumerate(paths)])
+    for q, c in enumerate((LT, LA)):
+        bound = 4.0 * n_rows * U * final[:, q]
+        e = np.abs(lrec[..., c] - wl[..., c]).max(axis=(1, 2))
+        worst[("TTIME", "ATTEN")[q] + " / final"] = float((e / final[:, q]).max())
+        worst[("TTIME", "ATTEN")[q] + " / bound"] = float((e / bound).max())
+    print(f"{what}: {int(count.sum())} crossings ({int((lrec[..., LEG] >= 1).sum())} behind a bounce) equal the restatement of the sampled path; worst "
+          + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert all(v <= 1.0 for k, v in worst.items() if not k.endswith("final")), (what, worst)
+    return wc, wl
+
+
+def _toy_fan(bounces=2, range_limit=500.0):
+    th, ph = _two_azimuths()
+    return th, ph, dict(bounces=bounces, calc_amp=1, range_limit=range_limit)
+
+
+@pytest.mark.parametrize("eq", ALL_SETS)
+def test_crossings_equal_the_restatement_of_the_sampled_path(G, legs_fixture, eq, tmp_path):
+    """the fans of the legs fixture (ToyAtmo at two azimuths, the ragged grids), two bounces"""
+    th, ph, params = _legs_fan(eq, legs_fixture)
+    rec, count, lrec, paths, n_rows = _pair(G, eq, tmp_path, th, ph, LEVELS, **params)
+    _check_against_path(eq, rec, count, lrec, paths, n_rows, LEVELS, H.EQ_NAMES[eq])
+    assert (lrec[..., LEG] == 2.0).any()
+
+
+@pytest.mark.parametrize("eq", [H.EQ_3D, H.EQ_GLOBAL])
+def test_chunk_seams_equal_the_sampled_path(G, eq, tmp_path):
+    """64-row chunks in both contexts: crossings on carry rows, sample events on every row of every chunk (test_crossings_do_not_depend_on_the_launch_plan
+    proves this plan equal to the default one; this proves both equal to the path)"""
+    th, ph, params = _toy_fan()
+    rec, count, lrec, paths, n_rows = _pair(G, eq, tmp_path, th, ph, LEVELS, opts={"GEOAC_S_ROWS": "64"}, **params)
+    _check_against_path(eq, rec, count, lrec, paths, n_rows, LEVELS, f"{H.EQ_NAMES[eq]}, 64-row chunks")
+
+
+EIGHT = [5.0, 12.0, 20.0, 35.0, 50.0, 70.0, 90.0, 110.0]
+
+
+@pytest.mark.parametrize("eq", [H.EQ_3D, H.EQ_GLOBAL])
+def test_every_instantiation_gives_the_same_crossings(G, eq, tmp_path):
+    """k_levels<8> against the sampled path; k_levels<1> .. <7> with the first L of the eight levels: every level's count and records the same bits as its
+    slice of the eight-level run, the launch's records unchanged"""
+    th, ph, params = _toy_fan(bounces=1, range_limit=300.0)
+    rec, count, lrec, paths, n_rows = _pair(G, eq, tmp_path, th, ph, EIGHT, **params)
+    _check_against_path(eq, rec, count, lrec, paths, n_rows, EIGHT, f"{H.EQ_NAMES[eq]}, 8 levels")
+    assert (count > 0).any(axis=0).all(), "every level is crossed by some ray"
+    with G.options(GEOAC_ABS_TABLE="0"):
+        for L in range(1, 8):
+            r, _, c, lr, _ = _toy(G, eq, th, ph, levels=EIGHT[:L], **params)
+            assert c.shape == (len(th), L) and np.array_equal(c, count[:, :L]), L
+            assert np.array_equal(lr.view(np.uint64), lrec[:, :L].view(np.uint64)), L
+            assert np.array_equal(r.view(np.uint64), rec.view(np.uint64)), L
+
+
+@pytest.mark.parametrize("eq", [H.EQ_3D, H.EQ_GLOBAL])
+def test_elevated_source_and_downward_launches(G, eq, tmp_path):
+    """source at 25 km, between the levels, in the stratospheric duct of ToyAtmo: rays launched below the horizontal cross 20 km downward first, on leg 0; the
+    steep ones reach the ground and come back up through the levels on leg 1, the shallow ones swing about 20 km until the range limit (hence cap = 32)"""
+    inc = np.array([-60.0, -40.0, -18.0, -8.0, 3.0, 20.0])
+    th, ph = np.tile(inc, 2), np.repeat([LR.PHI, 37.0], len(inc))
+    src = (25.0, 30.0, 0.0) if eq == H.EQ_GLOBAL else (0.0, 0.0, 25.0)
+    rec, count, lrec, paths, n_rows = _pair(G, eq, tmp_path, th, ph, LEVELS, cap=32, bounces=2, calc_amp=1, range_limit=400.0, src=src)
+    _check_against_path(eq, rec, count, lrec, paths, n_rows, LEVELS, f"{H.EQ_NAMES[eq]}, source at 25 km")
+    down = th < 0.0
+    assert (count[down, 0] >= 1).all() and (lrec[down, 0, 0, DIR] == -1.0).all() and (lrec[down, 0, 0, LEG] == 0.0).all()
+    assert (lrec[down, 0, 1, DIR] == 1.0).all() and (lrec[..., LEG] >= 1.0).any() and (count[:, 0] >= 4).any()
+
+
+@pytest.mark.parametrize("eq", [H.EQ_3D, H.EQ_GLOBAL])
+def test_a_row_exactly_on_a_level_counts_once(G, eq, tmp_path):
+    """levels set to the height of an ascending and of a descending interior row of one ray (azimuth 37, leg 0): the upward crossing is counted once, with
+    FRAC == 1.0 in the segment that ends on the row, the downward one once, with FRAC == 0.0 in the segment that starts on it, and the interpolated position
+    is the row's (a + 1.0 (b - a) is b where b - a is exact: asserted of the row chosen); every other count is that of levels 1 m higher.  Spherical set:
+    the level z must give r_earth + z == r bit for bit, which r - r_earth does (_check_against_path); were it not to, the set is left out with that printed."""
+    th, ph, params = _toy_fan(bounces=1, range_limit=500.0)
+    _, _, _, paths, _ = _pair(G, eq, tmp_path, th, ph, LEVELS, **params)
+    ray, hi = next(r for r in range(6, 12) if paths[r][0][0] > 0), LR.hidx(eq)      # the first ray at azimuth 37 whose first leg comes down to the ground
+    rows = paths[ray][0][1]
+    off = LR.R_EARTH if eq in LR.SPHERICAL else 0.0
+    h = rows[:, hi]
+    top = int(np.argmax(h))
+    i_up = next(i for i in range(2, top) if h[i] - off > 27.0)
+    i_dn = next(i for i in range(top + 1, len(h) - 2) if h[i] - off < 13.0)
+    z = []
+    for i in (i_dn, i_up):
+        near = [h[i] - off]
+        for _ in range(3):
+            near = [np.nextafter(near[0], -np.inf)] + near + [np.nextafter(near[-1], np.inf)]
+        hit = [v for v in near if off + v == h[i]]
+        if not hit:
+            print(f"{H.EQ_NAMES[eq]}: no level z with r_earth + z == r of row {i} within three steps of r - r_earth: left out")
+            return
+        z.append(float(hit[len(hit) // 2]))
+    rec, count, lrec, paths2, n_rows = _pair(G, eq, tmp_path, th, ph, z, **params)
+    assert np.array_equal(paths2[ray][0][1].view(np.uint64), rows.view(np.uint64))
+    _, wl = _check_against_path(eq, rec, count, lrec, paths2, n_rows, z, f"{H.EQ_NAMES[eq]}, levels on rows {i_dn} and {i_up}")
+    up = lrec[ray, 1, :count[ray, 1]]
+    dn = lrec[ray, 0, :count[ray, 0]]
+    on_up, on_dn = up[up[:, FRAC] == 1.0], dn[dn[:, FRAC] == 0.0]
+    assert len(on_up) == 1 and on_up[0, DIR] == 1.0 and on_up[0, LEG] == 0.0 and len(on_dn) == 1 and on_dn[0, DIR] == -1.0 and on_dn[0, LEG] == 0.0
+    assert (up[up[:, LEG] == 0.0][:, DIR] == 1.0).sum() == 1 and (dn[dn[:, LEG] == 0.0][:, DIR] == -1.0).sum() == 1, "the row on the level is counted once"
+    n_pos = 1 if eq in LR.SPHERICAL else 3                       # (latitude and longitude come back from degrees: _check_against_path)
+    a, b = rows[i_up - 1, :n_pos], rows[i_up, :n_pos]
+    assert (a + (b - a) == b).all(), "choose another row: b - a is not exact here"
+    assert np.array_equal(on_up[0, P0:P0 + n_pos].view(np.uint64), b.view(np.uint64))
+    assert np.array_equal(on_dn[0, P0:P0 + n_pos].view(np.uint64), rows[i_dn, :n_pos].view(np.uint64))
+    with G.options(GEOAC_ABS_TABLE="0"):
+        moved = _toy(G, eq, th, ph, levels=[v + 1e-3 for v in z], **params)
+    assert np.array_equal(moved[2], count), (moved[2], count)
 
 
 # ---------------------------------------------------------------- known answer

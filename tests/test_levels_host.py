@@ -1,6 +1,8 @@
 """CPU suite for level crossings (include/geoac_levels.h): the crossing rule of tests/levels_reference.py on the plain-C oracle's rows against the
-fixture made from the compiled reference's rows (tests/golden/levels_small.npz, tests/golden/make_golden_levels.py), and the validation of a level
-list through the ABI's host-only check - no device is needed for either."""
+fixture made from the compiled reference's rows (tests/golden/levels_small.npz, tests/golden/make_golden_levels.py); the numpy restatement of k_levels
+on every leg of the oracle's paths against the reference's crossings, times and attenuations of all four sets (tests/golden/levels_legs.npz), with five
+deliberately wrong restatements that the comparison must refuse; and the validation of a level list through the ABI's host-only check - no device is
+needed for any of it."""
 import ctypes
 import os
 
@@ -9,6 +11,7 @@ import pytest
 
 import harness as H
 import levels_reference as LR
+import rngdep_data as RD
 
 import geoac_amd as G
 
@@ -62,6 +65,74 @@ def test_restatement_on_oracle_rows_gives_the_fixture(fixture, eq):
             worst = max(worst, float(err.max()))
     print(f"{name}: largest position error of the oracle's crossings against the reference's {worst:.3e}")
     assert worst <= 1e-6
+
+
+# ---------------------------------------------------------------- every leg, four sets (tests/golden/levels_legs.npz)
+@pytest.fixture(scope="module")
+def legs_fixture():
+    return np.load(LR.LEGS_FIXTURE)
+
+
+_paths = {}
+
+
+def _oracle_paths(name, g, tmp_path_factory):
+    """every leg of the fixture's rays from the plain-C oracle's orc_trace_path, traced once per set and shared (read-only)"""
+    eq = LR.LEGS_SETS[name]
+    if name not in _paths:
+        th, ph = g[f"{name}_theta"], g[f"{name}_phi"]
+        if eq in (H.EQ_3D, H.EQ_GLOBAL):
+            O = H.Oracle(eq)
+            cfg = H.make_cfg(eq, bounces=2, calc_amp=True, range_limit=float(g[f"{name}_range_limit"]))
+        else:
+            glob = eq == H.EQ_GLOBAL_RNGDEP
+            O = H.Oracle(eq, met=None)
+            O.load_grid(*RD.write_grid_ragged(str(tmp_path_factory.mktemp("ragged")), glob, short_paths=False), z_grnd=RD.ragged_load_z_grnd(glob))
+            cfg = H.make_cfg(eq, bounces=2, calc_amp=True, src=tuple(g[f"{name}_src"]), z_grnd=float(g[f"{name}_z_grnd"]))
+        _paths[name] = [O.trace_path(cfg, t, p) for t, p in zip(th, ph)]
+        for legs in _paths[name]:
+            for _, rows, sums in legs:
+                rows.setflags(write=False); sums.setflags(write=False)
+    return _paths[name]
+
+
+def test_legs_fixture_is_conditioned(legs_fixture):
+    """what make_golden_levels.py asserts when it writes levels_legs.npz, read back"""
+    g = legs_fixture
+    for name, eq in list(LR.LEGS_SETS.items()) + [("3d_onrow", H.EQ_3D)]:
+        lev, leg = g[f"{name}_levels"], g[f"{name}_leg"]
+        assert (np.diff(lev) > 0).all() and int(g[f"{name}_cap_needed"]) == g[f"{name}_count"].max() <= 64
+        assert len(leg) == g[f"{name}_count"].sum() and (leg >= 1).sum() >= 6 and (leg == 2).any()
+        assert (np.abs(g[f"{name}_dab"][:, LR.hidx(eq)]) > 1e-6).all()
+        assert g[f"{name}_row"].shape == (len(leg), LR.PATHW[eq]) and (g[f"{name}_ttime"] > 0).all() and (g[f"{name}_atten"] > 0).all()
+        if name != "3d_onrow":
+            assert len(lev) == 3 and (lev == np.round(lev)).all()
+            assert (np.abs(g[f"{name}_turn"][:, None] - lev[None, :]) > 0.1).all() and float(g[f"{name}_sum_diff"]) <= 1e-12
+    on = g["3d_onrow_frac"]
+    assert ((on == 0.0) | (on == 1.0)).sum() == 2
+
+
+@pytest.mark.parametrize("name", list(LR.LEGS_SETS) + ["3d_onrow"])
+def test_restatement_on_oracle_paths_gives_the_legs_fixture(legs_fixture, tmp_path_factory, name):
+    """restate_k_levels on the oracle's rows and running sums, through the comparison the GPU suite puts k_levels through"""
+    eq = LR.LEGS_SETS[name.split("_")[0]]
+    paths = _oracle_paths(name.split("_")[0], legs_fixture, tmp_path_factory)
+    cap = int(legs_fixture[f"{name}_cap_needed"])
+    count, lrec = LR.restate_fan(eq, paths, legs_fixture[f"{name}_levels"], cap)
+    LR.compare_with_fixture(eq, count, lrec, legs_fixture, name=name)
+
+
+@pytest.mark.parametrize("mutation", LR.MUTATIONS)
+def test_comparison_refuses_a_wrong_restatement(legs_fixture, tmp_path_factory, mutation):
+    """each deliberately wrong k_levels (LR.MUTATIONS) fails compare_with_fixture on every set.  The swapped up rule differs from the right one only where
+    a row lies exactly on a level, so it is put to the set that has such rows (3d_onrow: FRAC 1.0 in the segment before becomes 0.0 in the one after)."""
+    for name in (["3d_onrow"] if mutation == "up_rule_swapped" else list(LR.LEGS_SETS)):
+        eq = LR.LEGS_SETS[name.split("_")[0]]
+        paths = _oracle_paths(name.split("_")[0], legs_fixture, tmp_path_factory)
+        count, lrec = LR.restate_fan(eq, paths, legs_fixture[f"{name}_levels"], int(legs_fixture[f"{name}_cap_needed"]), mutate=mutation)
+        with pytest.raises(AssertionError) as why:
+            LR.compare_with_fixture(eq, count, lrec, legs_fixture, name=name)
+        print(name, mutation, "refused:", why.value.args[0] if why.value.args else why.value)
 
 
 def test_restatement_counts_a_row_on_a_level_once():
