@@ -100,6 +100,148 @@ static int format_selftest(long n){
     cout << kName << ": -format_selftest: " << vals.size() * 2 << " conversions, " << bad << " mismatches" << '\n';
     return bad ? 1 : 0;
 }
+
+// ---- one output stream's share of a chunk of -prop text (run_prop: "the text of the files").  A chunk formats every row in the STICKY form (what the
+//      stream prints once its first setprecision(8) has happened) and, of its first row, also the FRESH form (the fields before the row's first
+//      setprecision(8) at precision 6); the writer picks.  The first row need not start the text: blank lines may stand before it - in the results
+//      stream one per azimuth without an arrival, in the raypath stream one per ray that ended within 25 steps of every leg (the reference samples
+//      rows m % 25 == 0, m < k) - so the row's offset is kept beside its length. ----
+struct StreamText {
+    string text;                       // sticky form of everything the chunk adds to the stream
+    size_t first_at = 0, first_len = 0;   // its first row is text[first_at .. first_at + first_len)
+    string first_fresh;                // that row as a stream prints it that has not seen a setprecision(8) yet
+    bool any = false;                  // the chunk has a row in this stream
+};
+// one row into st: `lead(d, p)` appends the fields printed before the row's first setprecision(8) at precision p, `rest(d)` the others and the '\n'
+template<class Lead, class Rest>
+static inline void stream_row(StreamText& st, int p_lead_sticky, Lead&& lead, Rest&& rest){
+    const size_t at = st.text.size();
+    lead(st.text, p_lead_sticky); rest(st.text);
+    if(!st.any){
+        st.any = true; st.first_at = at; st.first_len = st.text.size() - at;      // (at > 0 where blank lines came first)
+        lead(st.first_fresh, 6); rest(st.first_fresh);
+    }
+}
+// a chunk's text into its stream; `sticks`: the main switches its streams to precision 8 (the spherical mains), `switched`: this stream has seen its
+// first row.  Returns the bytes written.
+static uint64_t stream_emit(ostream& os, const StreamText& st, bool sticks, bool& switched){
+    if(st.any && sticks && !switched){
+        const size_t after = st.first_at + st.first_len;
+        os.write(st.text.data(), (streamsize)st.first_at);
+        os.write(st.first_fresh.data(), (streamsize)st.first_fresh.size());
+        os.write(st.text.data() + after, (streamsize)(st.text.size() - after));
+        switched = true;
+        return st.first_at + st.first_fresh.size() + (st.text.size() - after);
+    }
+    os.write(st.text.data(), (streamsize)st.text.size());
+    return st.text.size();
+}
+// the caustic files of a run: in the reference ONE ofstream object, opened on a leg's file and closed again for every leg of every ray
+// (GeoAcGlobal_main.cpp:258-287).  Its precision outlives the files, so only the first caustic row of the whole RUN is fresh, whichever file takes
+// it.  `first`: the file of the chunk's first caustic row in the order of the reference's loop (ray, leg, step), -1: the chunk has none.
+static uint64_t stream_emit_shared(ostream* const* os, const StreamText* st, size_t n, int first, bool sticks, bool& switched){
+    uint64_t bytes = 0;
+    for(size_t l = 0; l < n; l++){
+        bool sw = switched || (int)l != first;
+        bytes += stream_emit(*os[l], st[l], sticks, sw);
+    }
+    if(first >= 0) switched = true;
+    return bytes;
+}
+// -stream_selftest: synthetic chunks (no context, no device) through stream_row / stream_emit against one std::ostringstream that prints the same
+// sequence the way the reference mains do (default float format, precision 6, setprecision(8) at the third field of each row under the spherical
+// rule: GeoAcGlobal_main.cpp:304-324), for the spherical and the Cartesian precision rule.
+static int stream_selftest(){
+    struct Ev { int blanks_before; double a, b; int n; double c, d; int blanks_after; };      // blank lines, then (unless n < 0) a row `a b n c d`, then blank lines
+    // values whose 6- and 8-digit forms differ in text AND in length (3.12346 / 3.1234567), and a pair that prints alike (3 / -90)
+    const Ev R1 = {0, 3.1234567, -90.1234567, 0, 29.969232123, -3.376149876, 0}, R2 = {0, 7.1234567, -90.1234567, 1, 29.5, -6.830112345, 1},
+             R3 = {0, 3.0, -90.0, 0, 30.25, -2.5, 0};
+    auto behind = [](Ev e, int blanks){ e.blanks_before = blanks; return e; };
+    const Ev none1 = {1, 0, 0, -1, 0, 0, 0}, none0 = {0, 0, 0, -1, 0, 0, 0};
+    struct Case { const char* name; bool switched; vector<vector<Ev>> chunks; };
+    const vector<Case> cases = {
+        {"first row at offset 0",                       false, {{R1, R2}, {R1}}},
+        {"first row behind one blank line",             false, {{behind(R1, 1), R2, R3}}},
+        {"first row behind three blank lines",          false, {{behind(R1, 3), R2}, {behind(R3, 2)}}},
+        {"rowless chunk, then a row behind a blank line", false, {{none0, none1}, {none0, behind(R1, 1), R2}, {behind(R1, 1)}}},
+        {"stream already switched",                     true,  {{behind(R1, 2), R2}, {R1}}},
+        {"single-field lead behind two blank lines",    false, {{behind(R1, 2), R3}}},
+    };
+    int bad = 0, ran = 0;
+    char tmp[64];
+    auto num = [&](string& d, double v, int prec){ d.append(tmp, (size_t)fmt_g(tmp, v, prec)); };
+    for(const bool sticks : {true, false}) for(const Case& cs : cases){
+        const bool one_field = strncmp(cs.name, "single", 6) == 0;          // the raypath / caustic rows: one field before the setprecision(8)
+        ostringstream want, got;
+        if(cs.switched && sticks) want << setprecision(8);
+        bool switched = cs.switched;
+        uint64_t bytes = 0;
+        for(const auto& chunk : cs.chunks){
+            StreamText st;
+            for(const Ev& e : chunk){
+                for(int q = 0; q < e.blanks_before; q++){ want << '\n'; st.text += '\n'; }
+                if(e.n >= 0){
+                    want << e.a;
+                    if(!one_field){ want << '\t' << e.b; want << '\t' << e.n; }
+                    if(sticks) want << '\t' << setprecision(8) << e.c; else want << '\t' << e.c;
+                    want << '\t' << e.d << '\n';
+                    const int p_rest = sticks ? 8 : 6;
+                    stream_row(st, p_rest,
+                               [&](string& d, int p){ num(d, e.a, p); if(!one_field){ d += '\t'; num(d, e.b, p); d += '\t'; d += to_string(e.n); } },
+                               [&](string& d){ d += '\t'; num(d, e.c, p_rest); d += '\t'; num(d, e.d, p_rest); d += '\n'; });
+                }
+                for(int q = 0; q < e.blanks_after; q++){ want << '\n'; st.text += '\n'; }
+            }
+            bytes += stream_emit(got, st, sticks, switched);
+        }
+        ran++;
+        if(got.str() != want.str() || bytes != want.str().size()){
+            bad++;
+            cout << "MISMATCH " << (sticks ? "spherical" : "Cartesian") << " rule, " << cs.name << ": " << bytes << " bytes counted" << '\n'
+                 << "--- emitted" << '\n' << got.str() << "--- iostream" << '\n' << want.str() << "---" << '\n';
+        }
+    }
+    // three files behind one stream object (the caustic files): rows as (chunk, file, value ...) in the order of the reference's loop; the run's first row
+    // goes to file 1, file 0's first row comes later in the same chunk, file 2's in the next chunk
+    for(const bool sticks : {true, false}) for(const bool was_switched : {false, true}){
+        struct Row { int chunk, file; double a, c, d; };
+        const vector<Row> rows = { {0, 1, 45.133059, 30.929627, -2.547054}, {0, 0, 42.776312, 30.98529, -0.19063352}, {0, 1, 120.47084, 30.799437, -5.9083288},
+                                   {1, 2, 3.1234567, -90.1234567, 1242.4491}, {1, 0, 7.1234567, 29.5, 819.19983} };
+        ostringstream one;                        // the one stream object: what it prints is moved to the file it is open on
+        if(was_switched && sticks) one << setprecision(8);
+        string want[3];
+        ostringstream got[3];
+        ostream* os[3] = { &got[0], &got[1], &got[2] };
+        bool switched = was_switched;
+        uint64_t bytes = 0;
+        for(int chunk = 0; chunk < 2; chunk++){
+            StreamText st[3];
+            int first = -1;
+            for(const Row& r : rows) if(r.chunk == chunk){
+                one << r.a;
+                if(sticks) one << '\t' << setprecision(8) << r.c; else one << '\t' << r.c;
+                one << '\t' << r.d << '\n';
+                want[r.file] += one.str(); one.str("");
+                const int p_rest = sticks ? 8 : 6;
+                if(first < 0) first = r.file;
+                stream_row(st[r.file], p_rest, [&](string& d, int p){ num(d, r.a, p); },
+                           [&](string& d){ d += '\t'; num(d, r.c, p_rest); d += '\t'; num(d, r.d, p_rest); d += '\n'; });
+            }
+            bytes += stream_emit_shared(os, st, 3, first, sticks, switched);
+        }
+        ran++;
+        bool ok = bytes == want[0].size() + want[1].size() + want[2].size();
+        for(int f = 0; f < 3; f++) ok = ok && got[f].str() == want[f];
+        if(!ok){
+            bad++;
+            cout << "MISMATCH " << (sticks ? "spherical" : "Cartesian") << " rule, three files behind one stream object" << (was_switched ? ", already switched" : "") << '\n';
+            for(int f = 0; f < 3; f++) cout << "--- file " << f << " emitted" << '\n' << got[f].str() << "--- file " << f << " iostream" << '\n' << want[f];
+            cout << "---" << '\n';
+        }
+    }
+    cout << kName << ": -stream_selftest: " << ran << " cases, " << bad << " mismatches" << '\n';
+    return bad ? 1 : 0;
+}
 static vector<std::pair<string, string>> g_opts;
 static void parse_gpu_args(int argc, char* argv[]){
     const char* dbg = getenv("GEOAC_DEBUG_ENV");
@@ -448,23 +590,18 @@ static int run_prop(char* inputs[], int count){
     //      results row - has 6 digits, everything after 8.  Formatting is the whole cost of a WriteRays run (1.1 GB of text for 16 200 rays against
     //      0.1 s of GPU time), so a batch is cut into chunks of rays that are formatted on several threads into buffers - std::to_chars, the same
     //      `%.{p}g` digits as the streams' (self-test: -format_selftest) - and written in order.  A chunk cannot know whether an earlier one has already
-    //      switched a stream, so it formats the sticky form and, of its FIRST row per stream, also the fresh form; the writer picks. ----
-    struct StreamText { string text; size_t first_len = 0; string first_fresh; bool any = false; };      // text = sticky form; its first row is text[0 .. first_len)
-    struct ChunkText { string progress; StreamText ray, res; vector<StreamText> cau; };
+    //      switched a stream, so it formats the sticky form and, of its FIRST row per stream, also the fresh form; the writer picks (StreamText,
+    //      stream_row, stream_emit above; self-test: -stream_selftest). ----
+    struct ChunkText { string progress; StreamText ray, res; vector<StreamText> cau; int cau_first = -1; };      // cau_first: the leg of the chunk's first caustic row (rows come sorted by ray, leg, step)
     const int p_lead_sticky = kSph ? 8 : 6, p_rest = kSph ? 8 : 6;
     auto format_chunk = [&](long i0, long i1, long base, const vector<double>& rec, const vector<double>& smp, const vector<size_t>& smp_of_ray, ChunkText& out){
         out.cau.resize(WriteCaustics ? (size_t)legs : 0);
         char tmp[64];
         auto num = [&](string& d, double v, int prec){ d.append(tmp, (size_t)fmt_g(tmp, v, prec)); };
-        // one row into stream st: `lead` writes the fields printed before the row's first setprecision(8) at precision p, `rest` the others
-        auto row = [&](StreamText& st, auto&& lead, auto&& rest){
-            const size_t at = st.text.size();
-            lead(st.text, p_lead_sticky); rest(st.text);
-            if(!st.any){
-                st.any = true; st.first_len = st.text.size() - at;            // (at == 0)
-                lead(st.first_fresh, 6); rest(st.first_fresh);
-            }
-        };
+        // one row into stream st: `lead` writes the fields printed before the row's first setprecision(8) at precision p, `rest` the others.
+        // In every stream but the caustic ones the chunk's first row may start behind blank lines: the results stream gets one per azimuth and the
+        // raypath stream one per ray whether or not rows came with them (a ray that ends within 25 steps of each leg has no raypath row).
+        auto row = [&](StreamText& st, auto&& lead, auto&& rest){ stream_row(st, p_lead_sticky, lead, rest); };
         for(long i = i0; i < i1; i++){
             out.progress += "Plotting ray path w/ theta = "; num(out.progress, th[(size_t)i], 6); out.progress += ", phi = "; num(out.progress, ph[(size_t)i], 6);
             out.progress += kRngC ? ".\n" : "\n";
@@ -480,6 +617,7 @@ static int run_prop(char* inputs[], int count){
                 } else if(kind == 1 && WriteCaustics && leg < legs){
                     // (the range-dependent Cartesian main writes a literal 0.0 column before the time, :270-274; the sample row carries it)
                     const int nv = kSph ? 4 : (kRngC ? 5 : (kEq == GEOAC_EQ_3D ? 4 : 3));
+                    if(out.cau_first < 0) out.cau_first = leg;
                     row(out.cau[(size_t)leg], [&](string& d, int p){ num(d, v[0], p); },
                                               [&](string& d){ for(int q = 1; q < nv; q++){ d += '\t'; num(d, v[q], p_rest); } d += '\n'; });
                 }
@@ -510,20 +648,10 @@ static int run_prop(char* inputs[], int count){
     };
     // stream state across the whole run: has the stream seen its first setprecision(8) (spherical mains: its first row)?
     bool ray_switched = false, res_switched = false;
-    vector<char> cau_switched((size_t)legs, 0);
+    bool cau_switched = false;                                        // one stream object behind all the caustic files (stream_emit_shared)
     uint64_t text_bytes = 0;
     double text_seconds = 0.0;
-    auto emit = [&](ostream& os, const StreamText& st, bool& switched){
-        if(st.any && kSph && !switched){
-            os.write(st.first_fresh.data(), (streamsize)st.first_fresh.size());
-            os.write(st.text.data() + st.first_len, (streamsize)(st.text.size() - st.first_len));
-            text_bytes += st.first_fresh.size() + st.text.size() - st.first_len;
-            switched = true;
-        } else {
-            os.write(st.text.data(), (streamsize)st.text.size());
-            text_bytes += st.text.size();
-        }
-    };
+    auto emit = [&](ostream& os, const StreamText& st, bool& switched){ text_bytes += stream_emit(os, st, kSph, switched); };
     const int n_fmt_threads = max(1, g_fmt_threads > 0 ? g_fmt_threads : (int)min(16u, max(1u, std::thread::hardware_concurrency())));
     // one batch of rays [i0, i1) of the fan: rec = its records, smp = its sample rows (ray index relative to i0)
     auto write_batch = [&](long i0, long i1, const vector<double>& rec, const vector<double>& smp){
@@ -575,7 +703,10 @@ static int run_prop(char* inputs[], int count){
             cout.write(T.progress.data(), (streamsize)T.progress.size());
             if(WriteRays) emit(raypath, T.ray, ray_switched);
             emit(results, T.res, res_switched);
-            for(size_t l = 0; l < T.cau.size(); l++){ bool sw = cau_switched[l] != 0; emit(caustics[l], T.cau[l], sw); cau_switched[l] = sw ? 1 : 0; }
+            if(!T.cau.empty()){
+                vector<ostream*> cs; for(auto& c : caustics) cs.push_back(&c);
+                text_bytes += stream_emit_shared(cs.data(), T.cau.data(), T.cau.size(), T.cau_first, kSph, cau_switched);
+            }
             T = ChunkText();                                                // (release the text)
         }
         for(auto& t : pool) t.join();
@@ -1136,6 +1267,7 @@ static int run_eig(char* inputs[], int count, bool direct){
 
 int main(int argc, char* argv[]){
     if(argc >= 2 && strcmp(argv[1], "-format_selftest") == 0) return format_selftest(argc >= 3 ? atol(argv[2]) : 1000000L);
+    if(argc >= 2 && strcmp(argv[1], "-stream_selftest") == 0) return stream_selftest();
     if(argc < (kRng ? 5 : 3)){ usage(); return 0; }
     parse_gpu_args(argc, argv);
     if(strncmp(argv[1], "-prop", 5) == 0) return run_prop(argv, argc);

@@ -30,6 +30,25 @@ CASES = {
     # the second profile format on the jet profile (tests/jet_data.py): 2 x 2 fan from 12 km, where the wind is 30 / -22 m/s; azimuths 45 and 135: both wind components act along and across the rays
     "3d_jet": ("GeoAc3D", ["profile_format=zuvwTdp", "theta_min=25", "theta_max=41", "theta_step=16", "phi_min=45", "phi_max=135", "phi_step=90",
                            "bounces=0", "z_src=12", "rng_max=450"]),
+    # results files whose first azimuth(s) have no arrival row: the azimuth's blank line stands before the run's first row, which the spherical
+    # mains print with 6 digits in theta and phi (the stream is still fresh).  Non-round angles, so that the 6- and 8-digit forms differ.
+    # one blank line, then the first row (upwind azimuth -180.12: all four rays leave the 350 km range)
+    "global_late": ("GeoAcGlobal", ["theta_min=3.1234567", "theta_max=15.2", "theta_step=4", "phi_min=-180.1234567", "phi_max=-90", "phi_step=90",
+                                    "bounces=1", "rng_max=350", "WriteCaustics=True"]),
+    # two blank lines, then the first row
+    "global_late2": ("GeoAcGlobal", ["theta_min=3.1234567", "theta_max=15.2", "theta_step=4", "phi_min=-270.1234567", "phi_max=-90", "phi_step=90",
+                                     "bounces=1", "rng_max=350", "WriteRays=False", "WriteCaustics=True"]),
+    # 71 inclinations per azimuth: the first 64 rays (a whole chunk of the driver's text formatter) and seven more have no row
+    "global_late_chunks": ("GeoAcGlobal", ["theta_min=3.1234567", "theta_max=20", "theta_step=0.24", "phi_min=-180.1234567", "phi_max=-90", "phi_step=90",
+                                           "bounces=0", "rng_max=350", "WriteRays=False", "CalcAmp=False"]),
+    # the same in the RAYPATH stream: a ray's blank line comes whether or not the ray had a row, and rows are the steps m % 25 == 0, m < k.  With a
+    # range of 20 m the rays at 3.12 and 43.12 degrees end within 25 steps, the one at 83.12 degrees leaves one row: two blank lines, then a row whose
+    # height has 6 digits.  No ray comes down: the results stream never opens.
+    "global_late_rays": ("GeoAcGlobal", ["theta_min=3.1234567", "theta_max=84", "theta_step=40", "azimuth=-90.1234567", "bounces=0", "rng_max=0.02"]),
+    # spherical grid main (no rng_max there): the box limits are compared with radians as typed, so lon_max=0.03 ends the two eastward rays
+    # (azimuth 89.88 from lon_src = 1.25 deg) 45 km out, before they come down; the westward azimuth has three rows
+    "globalrd_late": ("GeoAcGlobal.RngDep", ["theta_min=10.1234567", "theta_max=30.2", "theta_step=20", "phi_min=-270.1234567", "phi_max=-90", "phi_step=180",
+                                             "bounces=1", "WriteRays=False", "WriteCaustics=True", "z_src=0.5", "lon_src=1.25", "lon_max=0.03"]),
 }
 # the profile a case reads where it is not ToyAtmo.met (kept as the file MET beside ARGS)
 CASE_MET = {"3d_jet": "JetAtmo.met"}

@@ -41,12 +41,31 @@ def _compare_files(got, want):
     return nsame, ntok
 
 
-@pytest.mark.parametrize("case", ["global", "3d", "2d", "cfg1", "global_norays", "3drd", "globalrd", "global+groups", "3drd+groups", "3drd+sub", "global+1thread", "globalrd+1thread", "3d_jet"])
+# cases whose first row of a stream stands behind blank lines (make_golden_cli.py): azimuths without an arrival before the first results row, rays
+# without a sample before the first raypath row
+LATE_CASES = ("global_late", "global_late2", "global_late_chunks", "global_late_rays", "globalrd_late")
+
+
+def _late_head(path, nfields):
+    """(empty lines between the header and the first data row, that row's first `nfields` fields as written - None where the file has no row)"""
+    lines = open(path).read().split("\n")
+    assert lines[0].startswith("#") and lines[-1] == ""
+    body = lines[1:-1]
+    n = 0
+    while n < len(body) and body[n] == "":
+        n += 1
+    return n, (body[n].split("\t")[:nfields] if n < len(body) else None)
+
+
+@pytest.mark.parametrize("case", ["global", "3d", "2d", "cfg1", "global_norays", "3drd", "globalrd", "global+groups", "3drd+groups", "3drd+sub", "global+1thread", "globalrd+1thread", "3d_jet",
+                                  "global_late", "global_late2", "global_late_chunks", "global_late_rays", "globalrd_late",
+                                  "global_late+groups", "global_late2+groups", "global_late+1thread", "global_late_chunks+1thread"])
 def test_cli_files_match_reference_binaries(case, tmp_path):
     """"+groups": the same fan integrated one azimuth group at a time (the path large WriteRays fans take: bounded sample list, text of
     group g written while group g+1 is on the GPU) must give the same files.  "+sub": the launch plan of saturated grid fans forced on the
     small one - one lane per ray, cooperative LDS-DMA gather, 512-row epochs in four sub-epochs handed from workgroup to workgroup - with the
-    raypath samples and caustics on"""
+    raypath samples and caustics on.  "*_late*": the first row of the results (or raypath) file stands behind the blank lines of azimuths (rays) that
+    gave none - one, two, behind a whole formatter chunk of rowless rays, in groups of one azimuth - and is the row a fresh stream prints"""
     env = dict(os.environ)
     gpu_args = []                  # arguments of the GPU build (geoac_cli.cpp: gpu_rays_per_batch=, gpu_opt=KEY:value -> geoac_set_option); the environment is not read
     if case.endswith("+groups"):
@@ -87,6 +106,23 @@ def test_cli_files_match_reference_binaries(case, tmp_path):
         same += s; tot += t
     print(f"{case}: {same}/{tot} tokens textually identical")
     assert same >= 0.995 * tot
+    if case in LATE_CASES:
+        # the point of these cases: the blank lines before a stream's first row are all there, and the fields that row prints before the stream's
+        # first setprecision(8) - launch angles (results) or a height (raypaths), at precision 6 - are the reference's bytes
+        for f in want_files:
+            if f.endswith("_results.dat"):
+                # theta and phi are inputs: no arithmetic stands behind them, so the bytes must be the reference's
+                got_head, want_head = _late_head(tmp_path / f, 2), _late_head(os.path.join(gold, f), 2)
+                print(f"{case}: {f}: {got_head} (reference: {want_head})")
+                assert got_head == want_head, f"{f}: {got_head} vs the reference's {want_head}"
+            elif f.endswith("_raypaths.dat"):
+                # the height is computed (compared above to the printed precision); here: the blank lines, and no more than precision 6 allows
+                (got_n, got_row), (want_n, want_row) = _late_head(tmp_path / f, 1), _late_head(os.path.join(gold, f), 1)
+                print(f"{case}: {f}: {got_n} {got_row} (reference: {want_n} {want_row})")
+                assert got_n == want_n and (got_row is None) == (want_row is None)
+                if want_row is not None:
+                    digits = got_row[0].lower().split("e")[0].replace("-", "").replace(".", "").lstrip("0")
+                    assert len(digits) <= 6, f"{f}: first row starts {got_row[0]!r}: more digits than a fresh stream prints"
 
 
 @pytest.mark.parametrize("binary", ["GeoAcGlobal", "GeoAc3D"])

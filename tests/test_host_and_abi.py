@@ -165,3 +165,20 @@ def test_text_formatter_prints_what_the_iostreams_print():
         pytest.skip("drivers not built")
     r = subprocess.run([exe, "-format_selftest", "200000"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0 and b" 0 mismatches" in r.stdout, r.stdout.decode()[-2000:]
+
+
+@pytest.mark.parametrize("name", ["GeoAcGlobal", "GeoAc3D"])
+def test_text_chunks_splice_into_a_stream_as_the_iostreams_print(name):
+    """a chunk of -prop text holds its rows in the form a stream prints after its first setprecision(8) and its first row also in the fresh form; the
+    writer splices the fresh row in where the stream has not switched yet.  That row need not start the chunk: blank lines (azimuths without an arrival,
+    rays without a sample) may come first.  -stream_selftest builds such chunks without a device - first row at offset 0, behind one and behind three
+    blank lines, behind a chunk without a row, in a stream that has switched already, with one and with three fields before the switch - under the
+    spherical and the Cartesian precision rule, and compares the bytes written, and their count, with one std::ostringstream printing the same sequence.
+    The caustic files are one stream object in the reference, opened leg by leg: of three such files only the run's first row is fresh (four more cases)"""
+    import subprocess
+    exe = os.path.join(H.ROOT, "geoac_amd", "bin", name)
+    if not os.path.exists(exe):
+        import __graft_entry__
+        __graft_entry__.build()
+    r = subprocess.run([exe, "-stream_selftest"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=60)
+    assert r.returncode == 0 and b"16 cases, 0 mismatches" in r.stdout, r.stdout.decode()[-4000:]
