@@ -14,4 +14,5 @@ from .api import (  # noqa: F401
     TubeSpec, tube_spec, tube_check, TUBE, TUBE_MAX_SPAN, TUBE_COOP_MIN,
     levels_check, LVL, LVL_STRIDE, MAX_LEVELS,
     LStationSpec, lstation_spec, lstation_check, LSTA, LSTA_STRIDE,
+    LevelRefineSpec, level_refine_spec, level_refine_check, LRF, LRF_STRIDE, LRF_STATUS,
 )

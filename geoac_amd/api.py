@@ -154,6 +154,32 @@ def refine_check(eqset, spec):
         raise GeoAcError(f"geoac_refine_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
 
 
+class LevelRefineSpec(ctypes.Structure):
+    """geoac_level_refine_spec (include/geoac_level_refine.h): round limit, shrink limit, tolerance [km], step cut [deg] and finite-difference
+    step [deg] of a level refinement"""
+    _fields_ = [("max_iter", ctypes.c_int), ("max_shrink", ctypes.c_int), ("tol", ctypes.c_double), ("step_max_deg", ctypes.c_double), ("probe_deg", ctypes.c_double)]
+
+
+LRF_STRIDE = 16
+LRF = dict(MEMBER=0, STATION=1, LEG=2, DIR=3, ORD=4, STATUS=5, ITER=6, THETA=7, PHI=8, MISS=9, TTIME=10, CELERITY=11, ATTEN=12, N0=13)
+LRF_STATUS = RFN_STATUS
+
+
+def level_refine_spec(max_iter=8, max_shrink=4, tol=0.1, step_max_deg=0.2, probe_deg=0.02):
+    """a LevelRefineSpec from plain values"""
+    return LevelRefineSpec(int(max_iter), int(max_shrink), float(tol), float(step_max_deg), float(probe_deg))
+
+
+def level_refine_check(eqset, spec):
+    """geoac_level_refine_check: host-only validation (no GPU needed); raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_level_refine_fault.restype = ctypes.c_char_p
+    rc = lib.geoac_level_refine_check(int(eqset), ctypes.byref(spec))
+    if rc:
+        fault = lib.geoac_level_refine_fault(int(eqset), ctypes.byref(spec))
+        raise GeoAcError(f"geoac_level_refine_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
+
+
 class TubeSpec(ctypes.Structure):
     """geoac_tube_spec (include/geoac_tubemap.h): the grid of a MapSpec, the lattice and triangle filters of a StationSpec, the band on a hit's
     interpolated turning height and the detection threshold of a tube map"""
@@ -695,6 +721,31 @@ class FanContext:
         """HIP-event times of the last refine() [ms]: its launches, its own kernels"""
         ms = (ctypes.c_double * 2)(0.0, 0.0)
         self._chk(self.lib.geoac_fan_refine_timing(self._h, ms))
+        return dict(launch_ms=ms[0], kernel_ms=ms[1])
+
+    # ---- level refinement (include/geoac_level_refine.h): rounds, probes, step rule and rows run on the device; nothing is computed here ----
+    def level_refine(self, spec=None, **kw):
+        """geoac_fan_level_refine of the current level-station lists (level_stations() after a lattice launch with levels): `spec` a LevelRefineSpec, or
+        the arguments of level_refine_spec().  Returns rows [n_seeds][LRF_STRIDE] (columns LRF, status values LRF_STATUS) and a dict of counters.  The
+        call replaces the context's launch angles and last launch by its own last round (n_rays becomes 3 * n_seeds when there are any)."""
+        if spec is None:
+            spec = level_refine_spec(**kw)
+        self._chk(self.lib.geoac_fan_level_refine(self._h, ctypes.byref(spec)))
+        n, it = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(self.lib.geoac_fan_level_refine_shape(self._h, ctypes.byref(n), ctypes.byref(it)))
+        n = n.value
+        rows = np.empty((n, LRF_STRIDE))
+        self._chk(self.lib.geoac_fan_level_refine_fetch(self._h, _p(rows)))
+        st = np.zeros(6, dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_level_refine_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
+        if n:
+            self.n_rays = 3 * n
+        return rows, dict(zip(("launches", "ray_members", "seeds", "converged", "stalled_or_limit", "lost_or_singular"), (int(v) for v in st)))
+
+    def level_refine_timing(self):
+        """HIP-event times of the last level_refine() [ms]: its launches, its own kernels"""
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        self._chk(self.lib.geoac_fan_level_refine_timing(self._h, ms))
         return dict(launch_ms=ms[0], kernel_ms=ms[1])
 
     # ---- tube maps (include/geoac_tubemap.h): the rasteriser runs on the device; nothing is computed here ----

@@ -26,6 +26,7 @@
 #include "geoac_tubemap_int.h"
 #include "geoac_refine_int.h"
 #include "geoac_lstations_int.h"
+#include "geoac_level_refine_int.h"
 #include "geoac_levels_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
@@ -253,6 +254,8 @@ struct geoac_ctx {
     void* rfn_state = nullptr;                    // station refinement (geoac_refine.hip): NULL until the first geoac_fan_refine
     void* lsta_state = nullptr;                   // level stations (geoac_lstations.hip): NULL until the first geoac_fan_level_stations
     std::vector<double> rfn_mem;                  // [M][GEOAC_RFN_MEMW] of the last geoac_rfn_view
+    void* lrf_state = nullptr;                    // level refinement (geoac_level_refine.hip): NULL until the first geoac_fan_level_refine
+    std::vector<double> lrf_src;                  // [M][2] of the last geoac_lrf_view
     std::vector<double> ens_u, ens_v;             // every member's winds on the host (K > 1), beside ens_T: the Mach numbers at the source the refinement needs
     std::string err;
 };
@@ -553,6 +556,7 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->tube_state){ geoac_tube_release(ctx->tube_state); ctx->tube_state = nullptr; }
     if(ctx->lsta_state){ geoac_lsta_release(ctx->lsta_state); ctx->lsta_state = nullptr; }
     if(ctx->rfn_state){ geoac_rfn_release(ctx->rfn_state); ctx->rfn_state = nullptr; }
+    if(ctx->lrf_state){ geoac_lrf_release(ctx->lrf_state); ctx->lrf_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->ev_row[0], &ctx->ev_row[1], &ctx->ev_row[2], &ctx->ev_m[0], &ctx->ev_m[1], &ctx->ev_m[2],
@@ -1969,6 +1973,23 @@ int geoac_rfn_view(geoac_ctx* ctx, GeoacRfnView* v){
     v->r_earth = ctx->prm.r_earth; v->z_grnd = ctx->prm.z_grnd;
     v->calc_amp = ctx->prm.calc_amp ? 1 : 0; v->mode = ctx->prm.mode;
     v->state = &ctx->rfn_state;
+    return GEOAC_OK;
+}
+
+// ... and geoac_level_refine.hip (geoac_level_refine_int.h): the same view and the members' source points in the stations' axes
+int geoac_lrf_view(geoac_ctx* ctx, GeoacLrfView* v){
+    int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
+    if(rc) return rc;
+    const int K = ctx->n_members, M = ctx->n_src * K;
+    const bool sph = (ctx->eqset == GEOAC_EQ_GLOBAL || ctx->eqset == GEOAC_EQ_GLOBAL_RNGDEP);
+    ctx->lrf_src.assign((size_t)M * 2, 0.0);
+    for(int m = 0; m < M; m++){
+        const double* src = ctx->n_src > 1 ? &ctx->sources[(size_t)(m / K) * 3] : ctx->prm.src;
+        ctx->lrf_src[(size_t)m * 2] = sph ? src[1] : src[0]; ctx->lrf_src[(size_t)m * 2 + 1] = sph ? src[2] : src[1];
+    }
+    v->n_members = M; v->src = ctx->lrf_src.data();
+    v->r_earth = ctx->prm.r_earth; v->mode = ctx->prm.mode;
+    v->state = &ctx->lrf_state;
     return GEOAC_OK;
 }
 

@@ -1,4 +1,5 @@
-// geoac_launch_int.h - what geoac_map.hip, geoac_stations.hip, geoac_tubemap.hip, geoac_refine.hip and geoac_lstations.hip do alike with a
+// geoac_launch_int.h - what geoac_map.hip, geoac_stations.hip, geoac_tubemap.hip, geoac_refine.hip, geoac_lstations.hip and
+// geoac_level_refine.hip do alike with a
 // context and with the HIP runtime: device buffers that grow, the status of a failed HIP call, grid sizes, the event pair behind a *_timing
 // function, and the first steps of every entry point that reads the last completed launch.  Plain functions; each file keeps its own state and
 // its own entry points.  (What the two list searches alone share, geoac_stations.hip and geoac_lstations.hip, is geoac_lattice_list.h.)

@@ -276,6 +276,17 @@ extern "C" int geoac_fan_level_stations_shape(geoac_ctx* ctx, int* n_members, in
     return GEOAC_OK;
 }
 
+extern "C" int geoac_lsta_coords_dev(geoac_ctx* ctx, const double** sta_dev, const int** level_of_dev, int* n_sta){
+    LBound b;
+    int rc = lbind_lists(ctx, "fan_level_refine", &b);
+    if(rc) return rc;
+    const double* tail = (const double*)b.st->lb.axes + b.st->lb.h_axes.size();          // axes: theta_ax | phi_ax | sta | level_of
+    if(sta_dev) *sta_dev = tail - 2 * (size_t)b.st->n_sta;
+    if(level_of_dev) *level_of_dev = (const int*)tail;
+    if(n_sta) *n_sta = b.st->n_sta;
+    return GEOAC_OK;
+}
+
 extern "C" int geoac_fan_level_stations_dev(geoac_ctx* ctx, int which, void** dev_ptr, size_t* bytes){
     LBound b;
     int rc = lbind_lists(ctx, "fan_level_stations_dev", &b);

@@ -9,4 +9,7 @@
 
 extern "C" void geoac_lsta_release(void* state);                                 // geoac_destroy: frees the level-station state (device current, stream idle)
 
+// device copies of the stations [n_sta][2] and of level_of [n_sta] of the current lists (GEOAC_E_INVALID without current lists)
+extern "C" int  geoac_lsta_coords_dev(geoac_ctx* ctx, const double** sta_dev, const int** level_of_dev, int* n_sta);
+
 #endif

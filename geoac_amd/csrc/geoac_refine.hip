@@ -12,8 +12,9 @@
 //   k_rfn_rows   one thread per seed, after the last launch: the row and the seed's levels.
 // The kernels' arguments live in a block of device memory (RfnDev): passed by value they would sit in scalar registers beside the loop state.
 //
-// The arithmetic is fixed by the header and restated in tests/refine_reference.py, elementary functions included: every product is rounded
-// before it is added, so this file is compiled with contraction off (the pragma below; the Makefile gives the same flag).
+// The arithmetic is fixed by the header and restated in tests/refine_reference.py, elementary functions included (geoac_rfn_series.h, which
+// geoac_level_refine.hip includes too): every product is rounded before it is added, so this file is compiled with contraction off (the pragma
+// below; the Makefile gives the same flag).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
@@ -27,12 +28,11 @@
 #include "geoac_stations_int.h"
 #include "geoac_refine_int.h"
 #include "geoac_tri_rule.h"
+#include "geoac_rfn_series.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-const double kRfnPi = 3.141592653589793238462643;
 
 struct RfnDev {
     const double* sta_rows; const unsigned* hits; // the station lists (read by k_rfn_seed only)
@@ -49,44 +49,6 @@ struct RfnDev {
     int M, F, n_sta, cap, n_seeds, legs;
     long long n_lists;
 };
-
-__device__ inline double rfn_sin(double x){
-    const double x2 = x * x;
-    double t = x, s = x;
-    for(int k = 1; k <= 14; k++){ t = -(t * x2) / (double)((2 * k) * (2 * k + 1)); s = s + t; }
-    return s;
-}
-__device__ inline double rfn_cos(double x){
-    const double x2 = x * x;
-    double t = 1.0, s = 1.0;
-    for(int k = 1; k <= 14; k++){ t = -(t * x2) / (double)((2 * k - 1) * (2 * k)); s = s + t; }
-    return s;
-}
-__device__ inline void rfn_sincosd(double a, double* sn, double* cs){
-    const double q = floor(a / 90.0 + 0.5);
-    const double r = (a - 90.0 * q) * kRfnPi / 180.0;
-    const double n = q - 4.0 * floor(q / 4.0);
-    const double s = rfn_sin(r), c = rfn_cos(r);
-    if(n == 0.0){ *sn = s; *cs = c; }
-    else if(n == 1.0){ *sn = c; *cs = -s; }
-    else if(n == 2.0){ *sn = -s; *cs = -c; }
-    else { *sn = -c; *cs = s; }
-}
-__device__ inline double rfn_asin(double s){
-    const bool low = s <= 0.5;
-    const double u = low ? s : sqrt((1.0 - s) / 2.0);
-    const double x2 = u * u;
-    double t = u, a = u;
-    for(int k = 1; k <= 30; k++){ t = ((t * x2) * (double)((2 * k - 1) * (2 * k - 1))) / (double)((2 * k) * (2 * k + 1)); a = a + t; }
-    return low ? a : kRfnPi / 2.0 - 2.0 * a;
-}
-__device__ inline double rfn_dist(double lat1, double lon1, double lat2, double lon2, double R){
-    const double a = rfn_sin(((lat2 - lat1) * kRfnPi / 180.0) / 2.0), b = rfn_sin((wrap180(lon2 - lon1) * kRfnPi / 180.0) / 2.0);
-    double h = a * a + (rfn_cos(lat1 * kRfnPi / 180.0) * rfn_cos(lat2 * kRfnPi / 180.0)) * (b * b);
-    if(h > 1.0) h = 1.0;
-    return (2.0 * R) * rfn_asin(sqrt(h));
-}
-__device__ inline bool rfn_finite(double v){ return v - v == 0.0; }
 
 __global__ void k_rfn_seed(const RfnDev* __restrict__ Dp){
     const RfnDev& D = *Dp;
