@@ -698,6 +698,17 @@ class FanContext:
         self._chk(self.lib.geoac_fan_level_stations_timing(self._h, ctypes.byref(ms)))
         return ms.value
 
+    # ---- what the two refinements' wrappers do alike: the six counters of a *_stats call as a dict, the two times of a *_timing call ----
+    def _rounds_stats(self, fn):
+        st = np.zeros(6, dtype=np.uint64)
+        self._chk(fn(self._h, st.ctypes.data_as(ctypes.c_void_p)))
+        return dict(zip(("launches", "ray_members", "seeds", "converged", "stalled_or_limit", "lost_or_singular"), (int(v) for v in st)))
+
+    def _rounds_timing(self, fn):
+        ms = (ctypes.c_double * 2)(0.0, 0.0)
+        self._chk(fn(self._h, ms))
+        return dict(launch_ms=ms[0], kernel_ms=ms[1])
+
     # ---- station refinement (include/geoac_refine.h): rounds, step rule and rows run on the device; nothing is computed here ----
     def refine(self, spec=None, **kw):
         """geoac_fan_refine of the current station lists (stations() after a calc_amp = 1 lattice launch): `spec` a RefineSpec, or the arguments of
@@ -711,17 +722,13 @@ class FanContext:
         n, F = n.value, F.value
         rows, level = np.empty((n, RFN_STRIDE)), np.empty((n, F))
         self._chk(self.lib.geoac_fan_refine_fetch(self._h, _p(rows), _p(level)))
-        st = np.zeros(6, dtype=np.uint64)
-        self._chk(self.lib.geoac_fan_refine_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
         if n:
             self.n_rays = n
-        return rows, level, dict(zip(("launches", "ray_members", "seeds", "converged", "stalled_or_limit", "lost_or_singular"), (int(v) for v in st)))
+        return rows, level, self._rounds_stats(self.lib.geoac_fan_refine_stats)
 
     def refine_timing(self):
         """HIP-event times of the last refine() [ms]: its launches, its own kernels"""
-        ms = (ctypes.c_double * 2)(0.0, 0.0)
-        self._chk(self.lib.geoac_fan_refine_timing(self._h, ms))
-        return dict(launch_ms=ms[0], kernel_ms=ms[1])
+        return self._rounds_timing(self.lib.geoac_fan_refine_timing)
 
     # ---- level refinement (include/geoac_level_refine.h): rounds, probes, step rule and rows run on the device; nothing is computed here ----
     def level_refine(self, spec=None, **kw):
@@ -736,17 +743,13 @@ class FanContext:
         n = n.value
         rows = np.empty((n, LRF_STRIDE))
         self._chk(self.lib.geoac_fan_level_refine_fetch(self._h, _p(rows)))
-        st = np.zeros(6, dtype=np.uint64)
-        self._chk(self.lib.geoac_fan_level_refine_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
         if n:
             self.n_rays = 3 * n
-        return rows, dict(zip(("launches", "ray_members", "seeds", "converged", "stalled_or_limit", "lost_or_singular"), (int(v) for v in st)))
+        return rows, self._rounds_stats(self.lib.geoac_fan_level_refine_stats)
 
     def level_refine_timing(self):
         """HIP-event times of the last level_refine() [ms]: its launches, its own kernels"""
-        ms = (ctypes.c_double * 2)(0.0, 0.0)
-        self._chk(self.lib.geoac_fan_level_refine_timing(self._h, ms))
-        return dict(launch_ms=ms[0], kernel_ms=ms[1])
+        return self._rounds_timing(self.lib.geoac_fan_level_refine_timing)
 
     # ---- tube maps (include/geoac_tubemap.h): the rasteriser runs on the device; nothing is computed here ----
     def tubemap(self, spec=None, **kw):

@@ -3,14 +3,15 @@
 // A round is one fan of three rays per seed - the trial and two probes, one launch angle each moved by h - through the existing launch path
 // (geoac_fan_set_angles, geoac_fan_launch with the level list still set: nothing of the launch plan is touched or known here) and one kernel
 // that applies the header's step rule to every seed from its own member's crossing records (geoac_fan_levels_dev).  Every member integrates
-// every ray; a seed reads one member's crossings, the other M - 1 are discarded (header, "Cost").
+// every ray; a seed reads one member's crossings, the other M - 1 are discarded (header, "Cost").  The seed list, the rounds and the step
+// rule are geoac_newton_rounds.h's, shared with geoac_refine.hip; this file's own are where a seed comes from (a level-station row), its
+// miss and Jacobian (finite differences of two probe rays' crossing points) and what a finished row holds.
 //
 // Three kernels:
 //   k_lrf_seed   one thread per (list, row): the kept rows of the level-station lists become the dense seed list, each at its list's prefix
-//                count plus its place in the list - list order, no atomics (k_rfn_seed's scheme).  The prefix counts are integers summed on
-//                the host from hits[M][n_sta].
-//   k_lrf_step   one thread per seed, after a round's launch: the branch walk of the three rays, miss, accept / reject, Newton step, the next
-//                trial and its probes; counts the seeds still active (the one integer the host reads per round).
+//                count (integers summed on the host from hits[M][n_sta]) plus its place in the list - list order, no atomics.
+//   k_lrf_step   one thread per seed, after a round's launch: the branch walk of the three rays, miss, the step rule, the next trial and its
+//                probes; counts the seeds still active (the one integer the host reads per round).
 //   k_lrf_rows   one thread per seed, after the last launch: the row.
 // The kernels' arguments live in a block of device memory (LrfDev), as RfnDev does.  No LDS; the walk's state is a handful of registers.
 //
@@ -26,8 +27,6 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cmath>
-#include <stdint.h>
-#include <string.h>
 #include <string>
 #include <vector>
 
@@ -35,7 +34,7 @@
 #include "geoac_launch_int.h"
 #include "geoac_lstations_int.h"
 #include "geoac_level_refine_int.h"
-#include "geoac_rfn_series.h"
+#include "geoac_newton_rounds.h"
 
 #pragma clang fp contract(off)
 
@@ -43,52 +42,43 @@ namespace {
 
 enum { LRF_META = 6 };                            // ints per seed in LrfDev::meta
 
-struct LrfDev {
-    const double* lsta_rows; const unsigned* hits; // the level-station lists (read by k_lrf_seed only)
-    const unsigned* offs;                         // [n_lists]: seeds before the list
-    const double* sta; const int* level_of;       // [n_sta][2], [n_sta]: copies of this call's own
+struct LrfDev : RoundsDev {
+    enum { RAYS = 3 };
+    const double* lsta_rows;                      // the level-station lists' rows (read by k_lrf_seed only)
+    const int* level_of;                          // [n_sta]: a copy of this call's own
     const double* src;                            // [M][2]: the members' source points in the stations' axes
     int* meta;                                    // [n_seeds][LRF_META]: member, station, level, leg, direction (0 up, 1 down), ordinal
-    double* trial;                                // [2][3 * n_seeds]: theta | phi of the next launch, ray j * n_seeds + i
-    double* best;                                 // [5][n_seeds]: b_th | b_ph | b_miss | d_th | d_ph
-    int* state;                                   // [3][n_seeds]: status (0: active) | shrink counter | rounds used
-    unsigned* active;
     double* rows;
-    double tol, step_max, h, r_earth;
+    double h, r_earth;
     double r_level[GEOAC_MAX_LEVELS];             // r_earth + z_km[l]
-    int spherical, max_shrink;
-    int M, n_sta, cap, n_seeds, L, capL;
-    long long n_lists;
-};
+    int L, capL;
 
-// the three rays of seed i (< N) in the next launch: ray j * N + i < 3 * N; theta at trial[ray], phi at trial[3 * N + ray]
-__device__ inline void lrf_set_trial(const LrfDev& D, long long i, double th, double ph){
-    const long long N = D.n_seeds;
-    D.trial[i] = th;              D.trial[3 * N + i] = ph;
-    D.trial[N + i] = th + D.h;    D.trial[4 * N + i] = ph;
-    D.trial[2 * N + i] = th;      D.trial[5 * N + i] = ph + D.h;
-}
+    struct Seed { const int* me; double s0, s1, c0, c1; };               // the seed's meta row, its station, the trial ray's crossing point
+    // the three rays of seed i (< N) in the next launch: ray j * N + i < 3 * N; theta at trial[ray], phi at trial[3 * N + ray]
+    __device__ void set_trial(long long i, double th, double ph) const {
+        const long long N = n_seeds;
+        trial[i] = th;              trial[3 * N + i] = ph;
+        trial[N + i] = th + h;      trial[4 * N + i] = ph;
+        trial[2 * N + i] = th;      trial[5 * N + i] = ph + h;
+    }
+    __device__ double miss(long long i, const double* lrec, const int* lcount, Seed* S) const;
+    __device__ bool newton(long long i, const Seed& S, double th, double ph, const double* lrec, const int* lcount, double* d_th, double* d_ph) const;
+};
 
 __global__ void k_lrf_seed(const LrfDev* __restrict__ Dp){
     const LrfDev& D = *Dp;
     const long long n = D.n_lists * D.cap;
     const long long stride = (long long)gridDim.x * blockDim.x;
-    const double inf = __longlong_as_double(0x7ff0000000000000ll);
     for(long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += stride){        // t < n_lists * cap: a row of the lists
-        const long long list = t / D.cap;                        // < n_lists
-        const unsigned k = (unsigned)(t % D.cap);
-        const unsigned h = D.hits[list];
-        if(k >= (h < (unsigned)D.cap ? h : (unsigned)D.cap)) continue;
-        const long long i = (long long)D.offs[list] + k;         // < n_seeds: offs[list] + min(hits, cap) <= the prefix count of the next list
+        const long long list = t / D.cap, i = seed_slot(D, list, (unsigned)(t % D.cap));          // list < n_lists
+        if(i < 0) continue;                                      // i < n_seeds from here on
         const double* row = D.lsta_rows + t * GEOAC_LSTA_STRIDE;
         const int s = (int)(list % D.n_sta);                     // < n_sta
         int* me = D.meta + LRF_META * i;
         me[0] = (int)(list / D.n_sta); me[1] = s; me[2] = D.level_of[s];
         me[3] = (int)row[GEOAC_LSTA_LEG]; me[4] = row[GEOAC_LSTA_DIR] > 0.0 ? 0 : 1; me[5] = (int)row[GEOAC_LSTA_ORD];
-        const long long N = D.n_seeds;
-        lrf_set_trial(D, i, row[GEOAC_LSTA_THETA], row[GEOAC_LSTA_PHI]);
-        D.best[i] = 0.0; D.best[N + i] = 0.0; D.best[2 * N + i] = inf; D.best[3 * N + i] = 0.0; D.best[4 * N + i] = 0.0;
-        D.state[i] = 0; D.state[N + i] = 0; D.state[2 * N + i] = 0;
+        D.set_trial(i, row[GEOAC_LSTA_THETA], row[GEOAC_LSTA_PHI]);
+        seed_init(D, i);
     }
 }
 
@@ -116,72 +106,45 @@ __device__ inline void lrf_point(const LrfDev& D, const double* R, double* c0, d
     else { *c0 = R[GEOAC_LVL_P0 + 0]; *c1 = R[GEOAC_LVL_P0 + 1]; }
 }
 
-// Newton step from the base crossing point and the two probes' records; false: SINGULAR
-__device__ inline bool lrf_newton(const LrfDev& D, double c0, double c1, const double* Rt, const double* Rp, double s0, double s1, double* d_th, double* d_ph){
+// miss of the trial's crossing point: ray i is the trial itself
+__device__ inline double LrfDev::miss(long long i, const double* lrec, const int* lcount, Seed* S) const {
+    const int* me = meta + LRF_META * i;
+    const double s0 = sta[2 * me[1]], s1 = sta[2 * me[1] + 1];              // station me[1] < n_sta
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    const double* R = lrf_branch(*this, lrec, lcount, me, i);
+    double c0 = 0.0, c1 = 0.0, miss = inf;
+    if(R){
+        lrf_point(*this, R, &c0, &c1);
+        if(spherical) miss = rfn_dist(c0, c1, s0, s1, r_level[me[2]]);      // level me[2] < L <= GEOAC_MAX_LEVELS
+        else { const double dx = s0 - c0, dy = s1 - c1; miss = sqrt(dx * dx + dy * dy); }
+        if(!(miss == miss)) miss = inf;
+    }
+    S->me = me; S->s0 = s0; S->s1 = s1; S->c0 = c0; S->c1 = c1;
+    return miss;
+}
+
+// Newton step from the base crossing point and the two probes' records (rays N + i and 2 * N + i); false: SINGULAR
+__device__ inline bool LrfDev::newton(long long i, const Seed& S, double, double, const double* lrec, const int* lcount, double* d_th, double* d_ph) const {
+    const double* Rt = lrf_branch(*this, lrec, lcount, S.me, n_seeds + i);
+    const double* Rp = lrf_branch(*this, lrec, lcount, S.me, 2ll * n_seeds + i);
     if(!Rt || !Rp) return false;
+    const double c0 = S.c0, c1 = S.c1, s0 = S.s0, s1 = S.s1;
     double ct0, ct1, cp0, cp1;
-    lrf_point(D, Rt, &ct0, &ct1);
-    lrf_point(D, Rp, &cp0, &cp1);
-    const double e0 = s0 - c0, a00 = (ct0 - c0) / D.h, a01 = (cp0 - c0) / D.h;
+    lrf_point(*this, Rt, &ct0, &ct1);
+    lrf_point(*this, Rp, &cp0, &cp1);
+    const double e0 = s0 - c0, a00 = (ct0 - c0) / h, a01 = (cp0 - c0) / h;
     double e1, a10, a11;
-    if(D.spherical){ e1 = wrap180(s1 - c1); a10 = wrap180(ct1 - c1) / D.h; a11 = wrap180(cp1 - c1) / D.h; }
-    else { e1 = s1 - c1; a10 = (ct1 - c1) / D.h; a11 = (cp1 - c1) / D.h; }
-    const double det = a00 * a11 - a01 * a10;
-    double dt = (a11 * e0 - a01 * e1) / det;
-    double dp = (a00 * e1 - a10 * e0) / det;
-    if(det == 0.0 || !rfn_finite(det) || !rfn_finite(dt) || !rfn_finite(dp)) return false;
-    if(dt > D.step_max) dt = D.step_max;
-    if(dt < -D.step_max) dt = -D.step_max;
-    if(dp > D.step_max) dp = D.step_max;
-    if(dp < -D.step_max) dp = -D.step_max;
+    if(spherical){ e1 = wrap180(s1 - c1); a10 = wrap180(ct1 - c1) / h; a11 = wrap180(cp1 - c1) / h; }
+    else { e1 = s1 - c1; a10 = (ct1 - c1) / h; a11 = (cp1 - c1) / h; }
+    double det, dt, dp;
+    solve(a00, a01, a10, a11, e0, e1, &det, &dt, &dp);
+    if(!cut(det, &dt, &dp, step_max)) return false;
     *d_th = dt; *d_ph = dp;
     return true;
 }
 
 __global__ void k_lrf_step(const LrfDev* __restrict__ Dp, const double* __restrict__ lrec, const int* __restrict__ lcount, int round){
-    const LrfDev& D = *Dp;
-    const long long N = D.n_seeds;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if(i >= N || D.state[i] != 0) return;                        // i < N from here on
-    const int* me = D.meta + LRF_META * i;
-    const double s0 = D.sta[2 * me[1]], s1 = D.sta[2 * me[1] + 1];          // station me[1] < n_sta
-    const double th = D.trial[i], ph = D.trial[3 * N + i];
-    const double inf = __longlong_as_double(0x7ff0000000000000ll);
-    const double* R = lrf_branch(D, lrec, lcount, me, i);        // ray i: the trial itself
-    double c0 = 0.0, c1 = 0.0, miss = inf;
-    if(R){
-        lrf_point(D, R, &c0, &c1);
-        if(D.spherical) miss = rfn_dist(c0, c1, s0, s1, D.r_level[me[2]]);          // level me[2] < L <= GEOAC_MAX_LEVELS
-        else { const double dx = s0 - c0, dy = s1 - c1; miss = sqrt(dx * dx + dy * dy); }
-        if(!(miss == miss)) miss = inf;
-    }
-    int status = 0;
-    D.state[2 * N + i] = round;
-    if(miss <= D.tol){
-        status = GEOAC_RFN_CONVERGED;
-        D.best[i] = th; D.best[N + i] = ph; D.best[2 * N + i] = miss;
-    } else if(round == 1 && miss == inf){
-        status = GEOAC_RFN_LOST;
-        D.best[i] = th; D.best[N + i] = ph;
-    } else if(round == 1 || miss < D.best[2 * N + i]){
-        double d_th = 0.0, d_ph = 0.0;
-        D.best[i] = th; D.best[N + i] = ph; D.best[2 * N + i] = miss;
-        D.state[N + i] = 0;
-        // (miss < inf here unless round == 1, and then miss == inf was LOST: the base ray holds its branch)
-        if(!lrf_newton(D, c0, c1, lrf_branch(D, lrec, lcount, me, N + i), lrf_branch(D, lrec, lcount, me, 2 * N + i), s0, s1, &d_th, &d_ph)) status = GEOAC_RFN_SINGULAR;
-        D.best[3 * N + i] = d_th; D.best[4 * N + i] = d_ph;
-    } else {
-        D.best[3 * N + i] = D.best[3 * N + i] / 2.0;
-        D.best[4 * N + i] = D.best[4 * N + i] / 2.0;
-        const int n = D.state[N + i] + 1;
-        D.state[N + i] = n;
-        if(n > D.max_shrink) status = GEOAC_RFN_STALLED;
-    }
-    D.state[i] = status;
-    if(status == 0){
-        lrf_set_trial(D, i, D.best[i] + D.best[3 * N + i], D.best[N + i] + D.best[4 * N + i]);
-        atomicAdd(D.active, 1u);
-    } else lrf_set_trial(D, i, D.best[i], D.best[N + i]);
+    rounds_step(*Dp, round, lrec, lcount);
 }
 
 __global__ void k_lrf_rows(const LrfDev* __restrict__ Dp, const double* __restrict__ lrec, const int* __restrict__ lcount){
@@ -190,14 +153,10 @@ __global__ void k_lrf_rows(const LrfDev* __restrict__ Dp, const double* __restri
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if(i >= N) return;                                           // i < N from here on
     const int* me = D.meta + LRF_META * i;
-    int status = D.state[i];
-    if(status == 0){ status = GEOAC_RFN_ITER_LIMIT; D.state[i] = status; }
     double* row = D.rows + i * GEOAC_LRF_STRIDE;
+    const int status = row_head(D, i, row, GEOAC_LRF_STATUS, GEOAC_LRF_ITER, GEOAC_LRF_THETA, GEOAC_LRF_PHI, GEOAC_LRF_MISS);
     row[GEOAC_LRF_MEMBER] = (double)me[0]; row[GEOAC_LRF_STATION] = (double)me[1]; row[GEOAC_LRF_LEG] = (double)me[3];
     row[GEOAC_LRF_DIR] = me[4] ? -1.0 : 1.0; row[GEOAC_LRF_ORD] = (double)me[5];
-    row[GEOAC_LRF_STATUS] = (double)status; row[GEOAC_LRF_ITER] = (double)D.state[2 * N + i];
-    row[GEOAC_LRF_THETA] = D.best[i]; row[GEOAC_LRF_PHI] = D.best[N + i];
-    row[GEOAC_LRF_MISS] = status == GEOAC_RFN_LOST ? -1.0 : D.best[2 * N + i];
     double tt = 0.0, cel = 0.0, att = 0.0, n0 = 0.0, n1 = 0.0, n2 = 0.0;
     // a CONVERGED seed was integrated again at its best angles in the final launch: ray i holds the branch there (no record: the zeros stay)
     const double* R = status == GEOAC_RFN_CONVERGED ? lrf_branch(D, lrec, lcount, me, i) : nullptr;
@@ -214,52 +173,25 @@ __global__ void k_lrf_rows(const LrfDev* __restrict__ Dp, const double* __restri
     row[GEOAC_LRF_N0 + 0] = n0; row[GEOAC_LRF_N0 + 1] = n1; row[GEOAC_LRF_N0 + 2] = n2;
 }
 
-struct LrfState {
-    void* buf = nullptr; size_t buf_cap = 0;              // every device array of a call, carved below
+struct LrfState : RoundsState {
     LrfDev h{};                                           // host copy of the argument block (alive while its copy runs)
     LrfDev* args = nullptr;
-    std::vector<unsigned> h_offs;
-    std::vector<double> h_src, h_trial;
-    unsigned long long gen = 0;                           // the context's invalidation counter the result was made at (0: none)
-    int n_seeds = 0, launches = 0;
-    double ms_launch = 0.0, ms_kernels = 0.0;
-    uint64_t stats[6] = {0, 0, 0, 0, 0, 0};
-    EventPair ev;
+    std::vector<double> h_src;
     size_t rows_bytes() const { return sizeof(double) * (size_t)n_seeds * GEOAC_LRF_STRIDE; }
 };
 
 const char* spec_fault(int eqset, const geoac_level_refine_spec* s, int* code){
-    *code = GEOAC_E_INVALID;
-    if(eqset < GEOAC_EQ_2D || eqset > GEOAC_EQ_GLOBAL_RNGDEP) return "unknown equation set";
-    if(eqset == GEOAC_EQ_2D){
-        *code = GEOAC_E_UNSUPPORTED;
-        return "not implemented for the 2-D set: it has neither level crossings nor level-station lists to refine (geoac_lstations.h)";
-    }
-    if(!s) return "spec is NULL";
-    if(s->max_iter < 1 || s->max_iter > GEOAC_RFN_MAX_ITER) return "max_iter must be in 1 .. 32";
-    if(s->max_shrink < 0 || s->max_shrink > GEOAC_RFN_MAX_SHRINK) return "max_shrink must be in 0 .. 16";
-    if(!std::isfinite(s->tol) || !(s->tol > 0.0)) return "tol must be finite and > 0";
-    if(!std::isfinite(s->step_max_deg) || !(s->step_max_deg > 0.0)) return "step_max_deg must be finite and > 0";
+    if(const char* fault = rounds_spec_fault(eqset, s, "not implemented for the 2-D set: it has neither level crossings nor level-station lists to refine (geoac_lstations.h)", code))
+        return fault;
     if(!std::isfinite(s->probe_deg) || !(s->probe_deg > 0.0) || s->probe_deg > 1.0) return "probe_deg must be finite, > 0 and <= 1";
     return nullptr;
 }
 
-struct Bound { geoac_ctx* ctx; GeoacLrfView v; LrfState* st; };
-
-// (not bind_launch: geoac_fan_level_refine has its own message for a context without current lists, and the fetches ask for a current result)
-int bind(geoac_ctx* ctx, const char* what, Bound* b){
-    if(!ctx) return GEOAC_E_INVALID;
-    b->ctx = ctx;
-    int rc = geoac_lrf_view(ctx, &b->v);
-    if(rc) return rc;
-    b->st = (LrfState*)*b->v.state;
-    if(hipSetDevice(b->v.map.device) != hipSuccess) return geoac_map_fail(ctx, GEOAC_E_HIP, (std::string(what) + ": hipSetDevice failed").c_str());
-    return GEOAC_OK;
-}
+using Bound = RoundsBound<GeoacLrfView, LrfState>;
 
 // a current result, or GEOAC_E_INVALID.  (geoac_set_levels does not move the invalidation counter: the crossing tables answer for it.)
 int bind_result(geoac_ctx* ctx, const char* what, Bound* b){
-    int rc = bind(ctx, what, b);
+    int rc = rounds_bind(ctx, what, geoac_lrf_view, b);
     if(rc) return rc;
     if(!b->st || b->st->gen == 0 || b->st->gen != b->v.map.gen || geoac_fan_levels_dev(ctx, nullptr, nullptr, nullptr, nullptr) != GEOAC_OK)
         return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": no level refinement result, or a launch, new angles, an atmosphere upload, geoac_set_sources, "
@@ -267,17 +199,9 @@ int bind_result(geoac_ctx* ctx, const char* what, Bound* b){
     return GEOAC_OK;
 }
 
-size_t up256(size_t n){ return (n + 255) / 256 * 256; }
-
 }  // namespace
 
-extern "C" void geoac_lrf_release(void* state){
-    LrfState* st = (LrfState*)state;
-    if(!st) return;
-    if(st->buf) hipFree(st->buf);
-    st->ev.release();
-    delete st;
-}
+extern "C" void geoac_lrf_release(void* state){ rounds_release<LrfState>(state); }
 
 extern "C" const char* geoac_level_refine_fault(int eqset, const geoac_level_refine_spec* spec){
     int code;
@@ -292,7 +216,7 @@ extern "C" int geoac_level_refine_check(int eqset, const geoac_level_refine_spec
 extern "C" int geoac_fan_level_refine(geoac_ctx* ctx, const geoac_level_refine_spec* spec){
     const char* what = "fan_level_refine";
     Bound b;
-    int rc = bind(ctx, what, &b);
+    int rc = rounds_bind(ctx, what, geoac_lrf_view, &b);
     if(rc) return rc;
     int code;
     if(const char* fault = spec_fault(b.v.map.eqset, spec, &code)) return geoac_map_fail(ctx, code, (std::string("fan_level_refine: ") + fault).c_str());
@@ -314,38 +238,24 @@ extern "C" int geoac_fan_level_refine(geoac_ctx* ctx, const geoac_level_refine_s
     void* d_hits = nullptr; void* d_rows = nullptr; const double* d_sta = nullptr; const int* d_level_of = nullptr; size_t bytes = 0;
     if((rc = geoac_fan_level_stations_dev(ctx, 0, &d_hits, &bytes)) || (rc = geoac_fan_level_stations_dev(ctx, 1, &d_rows, &bytes)) ||
        (rc = geoac_lsta_coords_dev(ctx, &d_sta, &d_level_of, nullptr))) return rc;
-    // seeds before every list: integer prefix counts of min(hits, cap), on the host
     const long long n_lists = (long long)M * n_sta;
-    std::vector<unsigned> hits((size_t)n_lists);
-    GEOAC_CHK(what, hipMemcpyAsync(hits.data(), d_hits, sizeof(unsigned) * (size_t)n_lists, hipMemcpyDeviceToHost, s));
-    GEOAC_CHK(what, hipStreamSynchronize(s));
-    std::vector<unsigned> offs((size_t)n_lists);
+    std::vector<unsigned> offs;
     long long n_seeds = 0;
-    for(long long l = 0; l < n_lists; l++){
-        offs[(size_t)l] = (unsigned)n_seeds;
-        n_seeds += hits[(size_t)l] < (unsigned)cap ? hits[(size_t)l] : (unsigned)cap;
-        if(3 * n_seeds * M > GEOAC_RFN_MAX_RAY_MEMBERS)
-            return geoac_map_fail(ctx, GEOAC_E_CAPACITY, ("fan_level_refine: more than " + std::to_string(GEOAC_RFN_MAX_RAY_MEMBERS) + " ray-members per round (3 rays x seeds x " + std::to_string(M) +
-                                                          " members: every member integrates every seed and its two probes); refine fewer stations or members at a time").c_str());
-    }
-    if(!*b.v.state) *b.v.state = new LrfState();       // (the state is created only now: a refused call allocates nothing)
-    LrfState* st = b.st = (LrfState*)*b.v.state;
-    st->gen = 0;                                       // (no current result until this one is complete)
-    st->h_offs.swap(offs);
-    const size_t N = (size_t)n_seeds;
-    st->n_seeds = (int)n_seeds; st->launches = 0; st->ms_launch = 0.0; st->ms_kernels = 0.0;
-    for(int k = 0; k < 6; k++) st->stats[k] = 0;
-    st->stats[2] = (uint64_t)n_seeds;
+    GEOAC_CHK(what, count_seeds(d_hits, n_lists, cap, M, 3, s, &offs, &n_seeds));
+    if(n_seeds < 0)
+        return geoac_map_fail(ctx, GEOAC_E_CAPACITY, ("fan_level_refine: more than " + std::to_string(GEOAC_RFN_MAX_RAY_MEMBERS) + " ray-members per round (3 rays x seeds x " + std::to_string(M) +
+                                                      " members: every member integrates every seed and its two probes); refine fewer stations or members at a time").c_str());
+    LrfState* st = b.begin(&offs, n_seeds);
     if(n_seeds == 0){ st->gen = b.v.map.gen; return GEOAC_OK; }       // (an empty result; nothing was launched, the lists stay)
 
     // one device block: args | offs | sta | level_of | src | meta | trial | best | state | active | rows
-    size_t off = 0;
-    auto carve = [&](size_t n){ const size_t at = off; off += up256(n); return at; };
+    const size_t N = (size_t)n_seeds;
+    Carve carve;
     const size_t o_args = carve(sizeof(LrfDev)), o_offs = carve(sizeof(unsigned) * (size_t)n_lists), o_sta = carve(sizeof(double) * 2 * (size_t)n_sta),
                  o_lof = carve(sizeof(int) * (size_t)n_sta), o_src = carve(sizeof(double) * 2 * (size_t)M), o_meta = carve(sizeof(int) * LRF_META * N),
                  o_trial = carve(sizeof(double) * 6 * N), o_best = carve(sizeof(double) * 5 * N), o_state = carve(sizeof(int) * 3 * N), o_active = carve(sizeof(unsigned)),
                  o_rows = carve(sizeof(double) * GEOAC_LRF_STRIDE * N);
-    if(grow(&st->buf, &st->buf_cap, off)) return geoac_map_fail(ctx, GEOAC_E_NOMEM, "fan_level_refine: no device memory for the seeds");
+    if(grow(&st->buf, &st->buf_cap, carve.off)) return geoac_map_fail(ctx, GEOAC_E_NOMEM, "fan_level_refine: no device memory for the seeds");
     char* base = (char*)st->buf;
     st->args = (LrfDev*)(base + o_args);
     LrfDev& D = st->h;
@@ -359,7 +269,6 @@ extern "C" int geoac_fan_level_refine(geoac_ctx* ctx, const geoac_level_refine_s
     D.spherical = spherical(b.v.map.eqset) ? 1 : 0; D.max_shrink = spec->max_shrink;
     D.M = M; D.n_sta = n_sta; D.cap = cap; D.n_seeds = (int)n_seeds; D.L = L; D.capL = capL; D.n_lists = n_lists;
     st->h_src.assign(b.v.src, b.v.src + 2 * (size_t)M);
-    st->h_trial.resize(6 * N);
     GEOAC_CHK(what, hipMemcpyAsync(st->args, &D, sizeof(LrfDev), hipMemcpyHostToDevice, s));
     GEOAC_CHK(what, hipMemcpyAsync(base + o_offs, st->h_offs.data(), sizeof(unsigned) * (size_t)n_lists, hipMemcpyHostToDevice, s));
     GEOAC_CHK(what, hipMemcpyAsync(base + o_sta, d_sta, sizeof(double) * 2 * (size_t)n_sta, hipMemcpyDeviceToDevice, s));
@@ -371,48 +280,15 @@ extern "C" int geoac_fan_level_refine(geoac_ctx* ctx, const geoac_level_refine_s
     const unsigned n_blk = blocks_for(n_seeds, 64);
     const int n_rays = 3 * (int)n_seeds;
     const size_t n_rl = (size_t)M * n_rays * L;          // (member, ray, level) of a round's crossing tables
-    GeoacMapView mv{};
-    unsigned active = 1;
-    for(int round = 1; round <= spec->max_iter && active > 0; round++){
-        // the trial angles and their probes: device -> host -> geoac_fan_set_angles (48 bytes per seed).  The sync also ends the seed kernel's
-        // reads of the lists, which the launch invalidates.
-        GEOAC_CHK(what, hipMemcpyAsync(st->h_trial.data(), D.trial, sizeof(double) * 6 * N, hipMemcpyDeviceToHost, s));
-        GEOAC_CHK(what, hipStreamSynchronize(s));
-        if((rc = geoac_fan_set_angles(ctx, n_rays, st->h_trial.data(), st->h_trial.data() + 3 * N))) return rc;
-        if((rc = geoac_fan_launch(ctx))) return rc;
-        st->launches = round;
-        st->stats[0] = (uint64_t)round; st->stats[1] += (uint64_t)n_rays * (uint64_t)M;
-        double ms3[3] = {0, 0, 0}; uint64_t st3[3] = {0, 0, 0};
-        if(geoac_last_timing(ctx, ms3, st3) == GEOAC_OK) st->ms_launch += ms3[0];
-        if((rc = geoac_map_view(ctx, &mv))) return rc;
-        if((rc = geoac_fan_levels_dev(ctx, &lrec, &lrec_bytes, &lcount, &lcount_bytes))) return rc;
-        if(mv.M != M || mv.n_rays != n_rays || lcount_bytes != sizeof(int) * n_rl || lrec_bytes != sizeof(double) * GEOAC_LVL_STRIDE * n_rl * capL)
+    rc = run_rounds(b, what, D, 3, spec->max_iter, [&](int round, const GeoacMapView& v){
+        if(int e = geoac_fan_levels_dev(ctx, &lrec, &lrec_bytes, &lcount, &lcount_bytes)) return e;
+        if(v.M != M || v.n_rays != n_rays || lcount_bytes != sizeof(int) * n_rl || lrec_bytes != sizeof(double) * GEOAC_LVL_STRIDE * n_rl * capL)
             return geoac_map_fail(ctx, GEOAC_E_HIP, "fan_level_refine: the round's crossing tables do not have the shape of the seeds ([M][3 * n_seeds][L][cap])");
-        GEOAC_CHK(what, st->ev.start(s));
-        GEOAC_CHK(what, hipMemsetAsync(D.active, 0, sizeof(unsigned), s));
         hipLaunchKernelGGL(k_lrf_step, dim3(n_blk), dim3(64), 0, s, (const LrfDev*)st->args, (const double*)lrec, (const int*)lcount, round);
-        GEOAC_CHK(what, hipGetLastError());
-        GEOAC_CHK(what, st->ev.stop(s));
-        GEOAC_CHK(what, hipMemcpyAsync(&active, D.active, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        GEOAC_CHK(what, hipStreamSynchronize(s));
-        double t = 0; GEOAC_CHK(what, st->ev.ms(&t));
-        st->ms_kernels += t;
-    }
-    GEOAC_CHK(what, st->ev.start(s));
-    hipLaunchKernelGGL(k_lrf_rows, dim3(n_blk), dim3(64), 0, s, (const LrfDev*)st->args, (const double*)lrec, (const int*)lcount);
-    GEOAC_CHK(what, hipGetLastError());
-    GEOAC_CHK(what, st->ev.stop(s));
-    std::vector<int> status(N);
-    GEOAC_CHK(what, hipMemcpyAsync(status.data(), D.state, sizeof(int) * N, hipMemcpyDeviceToHost, s));
-    GEOAC_CHK(what, hipStreamSynchronize(s));
-    double t = 0; GEOAC_CHK(what, st->ev.ms(&t));
-    st->ms_kernels += t;
-    for(size_t i = 0; i < N; i++){
-        const int c = status[i];
-        st->stats[c == GEOAC_RFN_CONVERGED ? 3 : (c == GEOAC_RFN_STALLED || c == GEOAC_RFN_ITER_LIMIT ? 4 : 5)]++;
-    }
-    st->gen = mv.gen;
-    return GEOAC_OK;
+        return (int)GEOAC_OK;
+    });
+    if(rc) return rc;
+    return finish_rounds(b, what, D, [&]{ hipLaunchKernelGGL(k_lrf_rows, dim3(n_blk), dim3(64), 0, s, (const LrfDev*)st->args, (const double*)lrec, (const int*)lcount); });
 }
 
 extern "C" int geoac_fan_level_refine_shape(geoac_ctx* ctx, int* n_seeds, int* launches){
@@ -448,17 +324,11 @@ extern "C" int geoac_fan_level_refine_fetch(geoac_ctx* ctx, double* rows){
 extern "C" int geoac_fan_level_refine_timing(geoac_ctx* ctx, double ms[2]){
     Bound b;
     int rc = bind_result(ctx, "fan_level_refine_timing", &b);
-    if(rc) return rc;
-    if(!ms) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_level_refine_timing: NULL argument");
-    ms[0] = b.st->ms_launch; ms[1] = b.st->ms_kernels;
-    return GEOAC_OK;
+    return rc ? rc : rounds_timing(ctx, "fan_level_refine_timing", *b.st, ms);
 }
 
 extern "C" int geoac_fan_level_refine_stats(geoac_ctx* ctx, uint64_t stats[6]){
     Bound b;
     int rc = bind_result(ctx, "fan_level_refine_stats", &b);
-    if(rc) return rc;
-    if(!stats) return geoac_map_fail(ctx, GEOAC_E_INVALID, "fan_level_refine_stats: NULL argument");
-    for(int k = 0; k < 6; k++) stats[k] = b.st->stats[k];
-    return GEOAC_OK;
+    return rc ? rc : rounds_stats(ctx, "fan_level_refine_stats", *b.st, stats);
 }

@@ -9,7 +9,7 @@ import numpy as np
 
 import lstation_reference as LS
 from levels_reference import LVL
-from refine_reference import DIST, WRAP, CONVERGED, ITER_LIMIT, STALLED, LOST, SINGULAR, MAX_RAY_MEMBERS, spherical, bits  # noqa: F401
+from refine_reference import DIST, WRAP, CONVERGED, ITER_LIMIT, STALLED, LOST, SINGULAR, MAX_RAY_MEMBERS, spherical, bits, start, step_rule, tally  # noqa: F401
 
 LRF = dict(MEMBER=0, STATION=1, LEG=2, DIR=3, ORD=4, STATUS=5, ITER=6, THETA=7, PHI=8, MISS=9, TTIME=10, CELERITY=11, ATTEN=12, N0=13)
 LRF_STRIDE = 16
@@ -104,11 +104,10 @@ def reference_level_refine(eqset, hits, rows, sta, level_of, z_km, sp, integrate
     s0, s1 = sta[ss, 0], sta[ss, 1]
     r_level = r_earth + np.asarray(z_km, dtype=np.float64)[sl]
     h = sp["probe_deg"]
-    b_th, b_ph, b_miss, d_th, d_ph = np.zeros(n), np.zeros(n), np.full(n, np.inf), np.zeros(n), np.zeros(n)
-    status, shrink, used = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    run = start(n)
     count = lrec = None
     for rnd in range(1, sp["max_iter"] + 1):
-        if not (status == 0).any():
+        if not (run[5] == 0).any():
             break
         count, lrec = integrate(*fan_angles(th, ph, h))
         count, lrec = np.asarray(count).reshape((M, 3 * n, -1)), np.asarray(lrec)
@@ -119,28 +118,9 @@ def reference_level_refine(eqset, hits, rows, sta, level_of, z_km, sp, integrate
         Rt, has_t = branch_records(count, lrec, sm, sl, leg, direction, ordinal, 1)
         Rp, has_p = branch_records(count, lrec, sm, sl, leg, direction, ordinal, 2)
         c, ct, cp = (LS.crossing_points(eqset, r) for r in (R, Rt, Rp))
-        act = status == 0
-        miss = miss_of(eqset, c[0], c[1], present, s0, s1, r_level)
-        used[act] = rnd
-        conv = act & (miss <= sp["tol"])
-        lost = act & ~conv & (rnd == 1) & (miss == np.inf)
-        acc = act & ~conv & ~lost & ((rnd == 1) | (miss < b_miss))
-        rej = act & ~conv & ~lost & ~acc
-        take = conv | lost | acc
-        b_th, b_ph = np.where(take, th, b_th), np.where(take, ph, b_ph)
-        b_miss = np.where(conv | acc, miss, b_miss)
-        n_th, n_ph, ok = newton(eqset, c, ct, cp, has_t & has_p, s0, s1, h, sp["step_max_deg"])
-        d_th, d_ph = np.where(acc, n_th, d_th), np.where(acc, n_ph, d_ph)
-        shrink = np.where(acc, 0, shrink)
-        d_th, d_ph = np.where(rej, d_th / 2.0, d_th), np.where(rej, d_ph / 2.0, d_ph)
-        shrink = np.where(rej, shrink + 1, shrink)
-        status = np.where(conv, CONVERGED, status)
-        status = np.where(lost, LOST, status)
-        status = np.where(acc & ~ok, SINGULAR, status)
-        status = np.where(rej & (shrink > sp["max_shrink"]), STALLED, status)
-        live = status == 0
-        th = np.where(live, b_th + d_th, b_th)
-        ph = np.where(live, b_ph + d_ph, b_ph)
+        run, th, ph = step_rule(sp, rnd, th, ph, miss_of(eqset, c[0], c[1], present, s0, s1, r_level),
+                                newton(eqset, c, ct, cp, has_t & has_p, s0, s1, h, sp["step_max_deg"]), run)
+    b_th, b_ph, b_miss, _, _, status, _, used = run
     status = np.where(status == 0, ITER_LIMIT, status)
     out = np.zeros((n, LRF_STRIDE))
     out[:, LRF["MEMBER"]], out[:, LRF["STATION"]], out[:, LRF["LEG"]], out[:, LRF["DIR"]], out[:, LRF["ORD"]] = sm, ss, leg, direction, ordinal
@@ -161,10 +141,7 @@ def reference_level_refine(eqset, hits, rows, sta, level_of, z_km, sp, integrate
         out[:, LRF[name]] = np.where(c, v, 0.0)
     for q in range(3):
         out[:, LRF["N0"] + q] = np.where(c, R[:, P0 + 3 + q], 0.0)
-    stats["converged"] = int((status == CONVERGED).sum())
-    stats["stalled_or_limit"] = int(((status == STALLED) | (status == ITER_LIMIT)).sum())
-    stats["lost_or_singular"] = int(((status == LOST) | (status == SINGULAR)).sum())
-    return out, stats, (count, lrec)
+    return out, tally(stats, status), (count, lrec)
 
 
 def assert_equal_bits(got, want, name="rows"):

@@ -151,6 +151,46 @@ def members(eqset, sources, mach=None):
     return mem
 
 
+def start(n):
+    """the running arrays of n seeds before their first round: b_th, b_ph, b_miss, d_th, d_ph, status, shrink, used"""
+    return (np.zeros(n), np.zeros(n), np.full(n, np.inf), np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64),
+            np.zeros(n, dtype=np.int64))
+
+
+def step_rule(sp, rnd, th, ph, miss, step, run):
+    """the header's step rule after the launch of round rnd at trials (th, ph): miss [n] (inf: no record), step = (n_th, n_ph, ok) the Newton step
+    of every seed, run the running arrays of start().  Returns the updated arrays and the next trials."""
+    b_th, b_ph, b_miss, d_th, d_ph, status, shrink, used = run
+    n_th, n_ph, ok = step
+    act = status == 0
+    used = np.where(act, rnd, used)
+    conv = act & (miss <= sp["tol"])
+    lost = act & ~conv & (rnd == 1) & (miss == np.inf)
+    acc = act & ~conv & ~lost & ((rnd == 1) | (miss < b_miss))
+    rej = act & ~conv & ~lost & ~acc
+    take = conv | lost | acc
+    b_th, b_ph = np.where(take, th, b_th), np.where(take, ph, b_ph)
+    b_miss = np.where(conv | acc, miss, b_miss)
+    d_th, d_ph = np.where(acc, n_th, d_th), np.where(acc, n_ph, d_ph)
+    shrink = np.where(acc, 0, shrink)
+    d_th, d_ph = np.where(rej, d_th / 2.0, d_th), np.where(rej, d_ph / 2.0, d_ph)
+    shrink = np.where(rej, shrink + 1, shrink)
+    status = np.where(conv, CONVERGED, status)
+    status = np.where(lost, LOST, status)
+    status = np.where(acc & ~ok, SINGULAR, status)
+    status = np.where(rej & (shrink > sp["max_shrink"]), STALLED, status)
+    live = status == 0
+    return (b_th, b_ph, b_miss, d_th, d_ph, status, shrink, used), np.where(live, b_th + d_th, b_th), np.where(live, b_ph + d_ph, b_ph)
+
+
+def tally(stats, status):
+    """the statuses of finished seeds into the stats dict"""
+    stats["converged"] = int((status == CONVERGED).sum())
+    stats["stalled_or_limit"] = int(((status == STALLED) | (status == ITER_LIMIT)).sum())
+    stats["lost_or_singular"] = int(((status == LOST) | (status == SINGULAR)).sum())
+    return stats
+
+
 def reference_refine(eqset, hits, rows, sta, sp, integrate, mem, r_earth=6370.0, z_grnd=0.0, level_of=None):
     """rows [n][16], level [n][F], stats dict and the final records of the refinement of station lists (hits, rows) at stations sta under spec dict sp.
     integrate(theta, phi) -> records [M][n][legs][32] of a launch of these angles; level_of() -> level table [M][F][n][legs] of the last launch
@@ -165,40 +205,19 @@ def reference_refine(eqset, hits, rows, sta, sp, integrate, mem, r_earth=6370.0,
         return np.zeros((0, RFN_STRIDE)), np.zeros((0, 1)), stats, None
     s0, s1 = sta[ss, 0], sta[ss, 1]
     rg = r_earth + z_grnd
-    b_th, b_ph, b_miss, d_th, d_ph = np.zeros(n), np.zeros(n), np.full(n, np.inf), np.zeros(n), np.zeros(n)
-    status, shrink, used = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    run = start(n)
     idx = np.arange(n)
     rec = None
     for rnd in range(1, sp["max_iter"] + 1):
-        if not (status == 0).any():
+        if not (run[5] == 0).any():
             break
         rec = np.asarray(integrate(th.copy(), ph.copy()))
         rec = rec.reshape((M, n) + rec.shape[-2:])
         stats["launches"] = rnd
         stats["ray_members"] += n * M
         R = rec[sm, idx, sl]
-        act = status == 0
-        miss = miss_of(eqset, R, s0, s1, rg)
-        used[act] = rnd
-        conv = act & (miss <= sp["tol"])
-        lost = act & ~conv & (rnd == 1) & (miss == np.inf)
-        acc = act & ~conv & ~lost & ((rnd == 1) | (miss < b_miss))
-        rej = act & ~conv & ~lost & ~acc
-        take = conv | lost | acc
-        b_th, b_ph = np.where(take, th, b_th), np.where(take, ph, b_ph)
-        b_miss = np.where(conv | acc, miss, b_miss)
-        n_th, n_ph, ok = newton(eqset, R, s0, s1, th, ph, mem[sm], rg, sp["step_max_deg"])
-        d_th, d_ph = np.where(acc, n_th, d_th), np.where(acc, n_ph, d_ph)
-        shrink = np.where(acc, 0, shrink)
-        d_th, d_ph = np.where(rej, d_th / 2.0, d_th), np.where(rej, d_ph / 2.0, d_ph)
-        shrink = np.where(rej, shrink + 1, shrink)
-        status = np.where(conv, CONVERGED, status)
-        status = np.where(lost, LOST, status)
-        status = np.where(acc & ~ok, SINGULAR, status)
-        status = np.where(rej & (shrink > sp["max_shrink"]), STALLED, status)
-        live = status == 0
-        th = np.where(live, b_th + d_th, b_th)
-        ph = np.where(live, b_ph + d_ph, b_ph)
+        run, th, ph = step_rule(sp, rnd, th, ph, miss_of(eqset, R, s0, s1, rg), newton(eqset, R, s0, s1, th, ph, mem[sm], rg, sp["step_max_deg"]), run)
+    b_th, b_ph, b_miss, _, _, status, _, used = run
     status = np.where(status == 0, ITER_LIMIT, status)
     if level_of is None:
         with np.errstate(all="ignore"):
@@ -222,10 +241,7 @@ def reference_refine(eqset, hits, rows, sta, sp, integrate, mem, r_earth=6370.0,
         out[:, RFN[name]] = np.where(c, v, 0.0)
     for f in range(F):
         lvl[:, f] = np.where(c, level[sm, f, idx, sl], 0.0)
-    stats["converged"] = int(c.sum())
-    stats["stalled_or_limit"] = int(((status == STALLED) | (status == ITER_LIMIT)).sum())
-    stats["lost_or_singular"] = int(((status == LOST) | (status == SINGULAR)).sum())
-    return out, lvl, stats, rec
+    return out, lvl, tally(stats, status), rec
 
 
 def bits(a):
