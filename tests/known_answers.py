@@ -4,7 +4,7 @@ in closed form, and the reference's own unused self-checks (GeoAc_EvalHamiltonia
 tests/test_oracle_known_answers.py (CPU suite) the oracle's: the same closed forms judge both."""
 import numpy as np
 
-from harness import EQ_2D, EQ_3D, EQ_GLOBAL, REC
+from harness import EQ_2D, EQ_3D, EQ_3D_RNGDEP, EQ_GLOBAL, REC
 
 GAM_R = 0.00040187            # c = sqrt(gamR T)  (G2S_Spline1D.cpp:332)
 R_EARTH = 6370.0
@@ -16,22 +16,31 @@ def isothermal_profile(T0=250.0, top=140.0, dz=0.1, scale_height=8.0, rho0=1.2e-
     return z, np.full_like(z, T0), np.zeros_like(z), np.zeros_like(z), rho0 * np.exp(-z / scale_height)
 
 
-def check_straight_rays(eq, rec, theta, phi, src, T0=250.0, scale_height=8.0, rtol=1e-9, amp_rtol=1e-7):
+DS_MIN = 0.001                # the reference's shortest step [km] (GeoAc.Parameters.cpp:19): the step it takes at the ground
+
+
+def check_straight_rays(eq, rec, theta, phi, src, T0=250.0, scale_height=8.0, rtol=1e-9, amp_rtol=1e-7, z_grnd=0.0):
     """isothermal windless medium, elevated source: rays launched downward arrive on the ground along their launch direction (Cartesian sets; the
     spherical set: in their great-circle plane, see below).
     Every arrival: the end point lies on the launch line (offset from it <= rtol x length), the slowness vector is the launch direction,
     travel time = length / c, and (Cartesian sets) the amplitude is spherical spreading 1 / (4 pi R) x sqrt(rho_arrival / rho_source)
-    (2-D set: the reference takes rho at the ground for the source's: factor 1).  Returns (arrivals, worst offset, worst time error, worst amplitude error)."""
+    (2-D set: the reference takes rho at the ground for the source's: factor 1).  The range-dependent Cartesian set keeps nu_x, nu_y in its state.
+    z_grnd: an arrival's end point is the first row BELOW the ground (GeoAc_CheckGround: z < z_grnd), and the step there is DS_MIN (GeoAc_Set_ds:
+    0.05 - 0.049 exp(-height / 0.75), floored): the 3-D sets' end points lie below z_grnd by more than 0 and at most DS_MIN, and the amplitude's density
+    is the one at that row's height (clamped to rho(0) below the profile, which is all that shows with z_grnd = 0).
+    Returns (arrivals, worst offset, worst time error, worst amplitude error)."""
     c = np.sqrt(GAM_R * T0)
     th, az = np.radians(theta), np.radians(phi)
     valid = rec[:, 0, REC["VALID"]] > 0
     assert valid.sum() >= 3 and (rec[~valid, 0, REC["BROKE"]] > 0).all()
     st = rec[:, 0, REC["STATE"]:REC["STATE"] + 6]
-    if eq == EQ_3D:
+    if eq in (EQ_3D, EQ_3D_RNGDEP):
         d = np.stack([np.cos(th) * np.sin(az), np.cos(th) * np.cos(az), np.sin(th)], axis=1)
         p0 = np.array(src, dtype=float)
         p = st[:, 0:3]
-        nu = np.stack([d[:, 0], d[:, 1], st[:, 3]], axis=1)          # nu_x, nu_y are constants of the ray: only nu_z is state
+        nu = np.stack([d[:, 0], d[:, 1], st[:, 3]], axis=1) if eq == EQ_3D else st[:, 3:6]          # stratified: nu_x, nu_y are constants of the ray, only nu_z is state
+        below = z_grnd - p[valid, 2]
+        assert (below > 0.0).all() and (below <= DS_MIN).all(), f"end points lie {below.min():.3e} .. {below.max():.3e} km below the ground"
     elif eq == EQ_2D:
         d = np.stack([np.cos(th), np.sin(th)], axis=1)
         p0 = np.array([0.0, src[0]])
@@ -78,9 +87,9 @@ def check_straight_rays(eq, rec, theta, phi, src, T0=250.0, scale_height=8.0, rt
         et = np.abs(tt * c / L - 1.0)
         assert et.max() <= rtol, f"travel time x c differs from the path length by {et.max():.3e}"
     ea = np.zeros(1)
-    if eq in (EQ_3D, EQ_2D):
-        z_src = src[2] if eq == EQ_3D else src[0]
-        dens = np.exp(0.5 * z_src / scale_height) if eq == EQ_3D else 1.0   # sqrt(rho(ground) / rho(source)); below-ground samples are clamped to rho(0)
+    if eq in (EQ_3D, EQ_3D_RNGDEP, EQ_2D):
+        z_src = src[0] if eq == EQ_2D else src[2]
+        dens = 1.0 if eq == EQ_2D else np.exp(0.5 * (z_src - np.maximum(p[valid, 2], 0.0)) / scale_height)   # sqrt(rho(arrival) / rho(source)); below-ground samples are clamped to rho(0)
         want = dens / (4.0 * np.pi * L)
         ea = np.abs(rec[:, 0, REC["AMP"]][valid] / want - 1.0)
         assert ea.max() <= amp_rtol, f"amplitude differs from spherical spreading by {ea.max():.3e}"

@@ -47,6 +47,11 @@ def _launch(G, L, tmpdir):
     th, ph, nt, nph = TC.lattice_of(L)
     if kind in ("3drd", "globalrd"):
         ctx = (TGR if kind == "3drd" else TGG)._ctx(MC.write_grid(kind, str(tmpdir)), **prm)
+    elif kind == "gridens":
+        ctx = G.FanContext(eq, device=0)
+        ctx.member_files = TC.write_grid_members(str(tmpdir))                        # (kept for the per-member check: written once)
+        ctx.load_grid_ensemble(ctx.member_files)
+        ctx.set_params(**prm)
     else:
         ctx = G.FanContext(eq, device=0)
         _upload(ctx, [_toy(eq) if raw is None else _device_arrays(eq, *raw) for raw in TC.profiles_of(L)])
@@ -100,6 +105,25 @@ def test_layers_equal_the_station_lists_at_the_centres(G, launches, name):
         assert not np.array_equal(got["level_max"][0, 0], got["level_max"][0, F - 1])
     if "detect" in got:
         assert got["detect"].max() >= 1
+    if TC.LAUNCHES[case["launch"]]["kind"] == "gridens":
+        _members_equal_plain_contexts(G, case, ctx.member_files, got, th, ph, sp)
+
+
+def _members_equal_plain_contexts(G, case, files, got, th, ph, sp):
+    """a grid ensemble: every member's layers are those of a plain context holding that member's grid (one lane per ray, as the ensemble integrates)"""
+    L = TC.LAUNCHES[case["launch"]]
+    assert got["count"].shape[0] == len(files) == 2
+    for m, f in enumerate(files):
+        with G.options(GRID_LANES="1"):
+            ctx = G.FanContext(L["eq"], device=0)
+        ctx.load_grid(*f)
+        ctx.set_params(**L["params"])
+        ctx.run(th, ph)
+        want = ctx.tubemap(**dict(sp, detect_db=np.nan))
+        ctx.close()
+        for name in want:
+            assert np.array_equal(SR.bits(got[name][m]), SR.bits(want[name][0])), (m, name)
+    assert not np.array_equal(SR.bits(got["ttime_min"][0]), SR.bits(got["ttime_min"][1]))          # (the members are different atmospheres)
 
 
 def test_filters_only_remove_hits(G, launches):

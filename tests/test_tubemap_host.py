@@ -147,7 +147,8 @@ def test_reference_on_an_identity_landing_map():
 @functools.lru_cache(maxsize=None)
 def _oracle(launch):
     import tempfile
-    return TC.oracle_tables(TC.LAUNCHES[launch], tempfile.mkdtemp())
+    member0 = _oracle("3drd")[0][0] if TC.LAUNCHES[launch]["kind"] == "gridens" else None
+    return TC.oracle_tables(TC.LAUNCHES[launch], tempfile.mkdtemp(), member0=member0)
 
 
 @pytest.mark.parametrize("name", sorted(TC.CASES))
@@ -162,6 +163,10 @@ def test_grid_literals_meet_the_conditions_on_the_oracle(name):
     G.tube_check(TC.LAUNCHES[case["launch"]]["eq"], G.tube_spec(**sp), th.size)
     ref = TR.reference_tubemap(TC.LAUNCHES[case["launch"]]["eq"], rec, th, ph, level, sp)
     print(name, "cells with COUNT 0 / 1 / >= 2:", TR.check_non_vacuity(ref, name), "most hits at a centre", int(ref["count"].max()))
+    if TC.LAUNCHES[case["launch"]]["kind"] == "gridens":
+        # both members reach the grid, and they are different atmospheres: a member read twice would not pass the GPU case
+        assert ref["count"].shape[0] == 2 and (ref["count"].reshape(2, -1) > 0).sum(axis=1).min() >= sp["n"][0] * sp["n"][1] // 4
+        assert not np.array_equal(ref["ttime_min"][0], ref["ttime_min"][1])
     if case.get("cooperative"):
         # cells several times smaller than the landing triangles: the reached cells outnumber the triangles of both legs several times over
         assert int((ref["count"][0] >= 1).sum()) >= 3 * 2 * 2 * (nt - 1) * (nph - 1)

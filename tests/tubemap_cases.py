@@ -7,6 +7,7 @@ import numpy as np
 import harness as H
 import map_cases as MC
 import map_reference as MR
+import rngdep_data as RD
 import station_cases as SC
 import tubemap_reference as TR
 from test_gpu_ensemble import _raw_members
@@ -28,7 +29,10 @@ LAUNCHES = {
     "sources2x2": dict(kind="sources", eq=H.EQ_GLOBAL, sources=TUBE_SOURCES, n_prof=2, params=ONE_BOUNCE),
     "freqs3": dict(kind="freqs", eq=H.EQ_GLOBAL, freqs=FREQS[:3], params=ONE_BOUNCE),
     "circle": dict(kind="plain", eq=H.EQ_GLOBAL, params=dict(ONE_BOUNCE, src=WRAP_SRC), lattice=CIRCLE_LATTICE),
+    "gridens2": dict(kind="gridens", eq=H.EQ_3D_RNGDEP, params=dict(bounces=1, calc_amp=1, mode=0, src=(0.0, 0.0, 0.0))),
 }
+# the K = 2 grid ensemble: the 5 x 5 grid of tests/rngdep_data.py and the same grid with weaker winds and a warmer atmosphere - (wind scale, T shift [K])
+GRID_MEMBERS = [(1.0, 0.0), (0.85, 3.0)]
 
 # grids (at most 32 x 48 cells).  The westward fan from (30, 0) lands at lat 27.8 .. 32.1, lon -6.1 .. -2.1 on leg 0 and lat 25.5 .. 34.1,
 # lon -12.5 .. -4.1 on leg 1; the Cartesian one at x -540 .. -205, |y| < 309 km and x -1081 .. -410, |y| < 617 km
@@ -59,6 +63,7 @@ CASES = {
     "sources2x2": dict(launch="sources2x2", spec=dict(GRID_2SRC, detect_db=MC.DETECT_AMP)),
     "freqs3": dict(launch="freqs3", spec=dict(GRID_GLOBAL, detect_db=-80.0)),
     "circle-wrap": dict(launch="circle", spec=dict(GRID_CIRCLE)),
+    "gridens2": dict(launch="gridens2", spec=dict(GRID_3DRD, detect_db=MC.DETECT_AMP)),
     "fine": dict(launch="global", spec=dict(GRID_FINE), cooperative=True),
     "coarse": dict(launch="global", spec=dict(GRID_COARSE)),
     "half-off": dict(launch="global", spec=dict(GRID_HALF_OFF)),
@@ -68,8 +73,25 @@ CASES = {
 }
 
 
+def write_grid_members(dirpath):
+    """the files of the grid ensemble's members, one directory each, written as tests/rngdep_data.py writes its grid (member 0: the same bytes);
+    returns [(prefix, locx, locy), ...]"""
+    import os
+    files = [RD.write_grid(os.path.join(dirpath, "m0"), short_paths=False)]
+    z, T, u, v, rho, p = RD.load_grid_columns()
+    for m, (w, dT) in enumerate(GRID_MEMBERS[1:], start=1):
+        prefix, locx, locy = RD.write_grid(os.path.join(dirpath, f"m{m}"), short_paths=False)
+        for i in range(len(RD.X_NODES)):
+            for j in range(len(RD.Y_NODES)):
+                with open(f"{prefix}{i * len(RD.Y_NODES) + j}.met", "w") as fh:
+                    for k in range(len(z)):
+                        fh.write(f"{z[k]:.10g} {T[i, j, k] + dT:.12g} {w * u[i, j, k]:.12g} {w * v[i, j, k]:.12g} {rho[i, j, k]:.12g} {p[k]:.10g}\n")
+        files.append((prefix, locx, locy))
+    return files
+
+
 def lattice_of(launch):
-    kw = launch.get("lattice") or (SC.PARITY_LATTICE_RD if launch["kind"] in ("3drd", "globalrd") else SC.PARITY_LATTICE)
+    kw = launch.get("lattice") or (SC.PARITY_LATTICE_RD if launch["kind"] in ("3drd", "globalrd", "gridens") else SC.PARITY_LATTICE)
     return SC.lattice(**kw)
 
 
@@ -86,8 +108,9 @@ def spec_of(case, nt, nph, **overrides):
     return TR.spec(n_theta=nt, n_phi=nph, **dict(case["spec"], **overrides))
 
 
-def oracle_tables(launch, tmpdir):
-    """the launch on the CPU oracle: rec [M][n_rays][legs][32], level [M][F][n_rays][legs] (numpy's log10), angles, lattice shape"""
+def oracle_tables(launch, tmpdir, member0=None):
+    """the launch on the CPU oracle: rec [M][n_rays][legs][32], level [M][F][n_rays][legs] (numpy's log10), angles, lattice shape.  member0: a grid
+    ensemble's member 0 is the "3drd" launch itself; a caller that holds those records [n_rays][legs][32] passes them and saves the oracle's minutes"""
     eq, kind, prm = launch["eq"], launch["kind"], launch["params"]
     th, ph, nt, nph = lattice_of(launch)
     cfg = dict(bounces=prm["bounces"], calc_amp=bool(prm["calc_amp"]))
@@ -113,6 +136,15 @@ def oracle_tables(launch, tmpdir):
         per_f = [O.fan(H.make_cfg(eq, freq=f, **cfg), th, ph)[1] for f in launch["freqs"]]
         recs.append(per_f[0])
         atten = np.stack([r[:, :, H.REC["ATTEN"]] for r in per_f])
+    elif kind == "gridens":
+        for m, files in enumerate(write_grid_members(str(tmpdir))):
+            if m == 0 and member0 is not None:
+                assert LAUNCHES["3drd"]["params"] == prm
+                recs.append(np.asarray(member0))
+                continue
+            O = H.Oracle(eq, met=None)
+            O.load_grid(*files)
+            recs.append(O.fan(H.make_cfg(eq, **cfg), th, ph)[1])
     else:
         O = H.Oracle(eq, met=None)
         O.load_grid(*MC.write_grid(kind, str(tmpdir)))
