@@ -14,5 +14,6 @@ from .api import (  # noqa: F401
     TubeSpec, tube_spec, tube_check, TUBE, TUBE_MAX_SPAN, TUBE_COOP_MIN,
     levels_check, LVL, LVL_STRIDE, MAX_LEVELS,
     LStationSpec, lstation_spec, lstation_check, LSTA, LSTA_STRIDE,
+    LTubeSpec, ltube_spec, ltube_check, LTUBE,
     LevelRefineSpec, level_refine_spec, level_refine_check, LRF, LRF_STRIDE, LRF_STATUS,
 )

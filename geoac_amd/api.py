@@ -215,6 +215,41 @@ def tube_check(eqset, spec, n_rays):
     return int(cells.value)
 
 
+class LTubeSpec(ctypes.Structure):
+    """geoac_ltube_spec (include/geoac_ltubemap.h): the grid of a MapSpec, the lattice, legs, ordinals and edge filter of an LStationSpec, and the
+    directions and levels of a level tube map"""
+    _fields_ = [("origin", ctypes.c_double * 2), ("step", ctypes.c_double * 2), ("n", ctypes.c_int * 2), ("wrap_lon", ctypes.c_int),
+                ("n_theta", ctypes.c_int), ("n_phi", ctypes.c_int), ("phi_periodic", ctypes.c_int), ("leg_min", ctypes.c_int), ("leg_max", ctypes.c_int),
+                ("ord_max", ctypes.c_int), ("edge_max", ctypes.c_double), ("dir_mask", ctypes.c_int), ("level_mask", ctypes.c_int)]
+
+
+LTUBE = dict(COUNT=0, TTIME_MIN=1, ATTEN_MIN=2, FIRST=3)
+_LTUBE_LAYERS = (("count", LTUBE["COUNT"], np.uint64), ("ttime_min", LTUBE["TTIME_MIN"], np.float64), ("atten_min", LTUBE["ATTEN_MIN"], np.float64),
+                 ("first", LTUBE["FIRST"], np.int64))
+
+
+def ltube_spec(origin, step, n, n_theta, n_phi, edge_max, level_mask, wrap_lon=False, phi_periodic=False, leg_min=0, leg_max=2**31 - 1, ord_max=1,
+               dir_mask=3):
+    """an LTubeSpec from plain values (edge_max has no default: it must be finite, it bounds the cells a crossing triangle can cover; level_mask
+    has none either: bit l selects level l of the launch's list)"""
+    return LTubeSpec((ctypes.c_double * 2)(*[float(v) for v in origin]), (ctypes.c_double * 2)(*[float(v) for v in step]), (ctypes.c_int * 2)(*[int(v) for v in n]),
+                     1 if wrap_lon else 0, int(n_theta), int(n_phi), 1 if phi_periodic else 0, int(leg_min), int(leg_max), int(ord_max), float(edge_max),
+                     int(dir_mask), int(level_mask))
+
+
+def ltube_check(eqset, spec, n_rays, n_levels):
+    """geoac_ltube_check: host-only validation (no GPU needed) against a launch of n_rays rays and n_levels levels; returns the cell count and the
+    number of selected levels, or raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_ltube_fault.restype = ctypes.c_char_p
+    cells, n_sel = ctypes.c_int64(0), ctypes.c_int(0)
+    rc = lib.geoac_ltube_check(int(eqset), ctypes.byref(spec), int(n_rays), int(n_levels), ctypes.byref(cells), ctypes.byref(n_sel))
+    if rc:
+        fault = lib.geoac_ltube_fault(int(eqset), ctypes.byref(spec), int(n_rays), int(n_levels))
+        raise GeoAcError(f"geoac_ltube_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
+    return int(cells.value), int(n_sel.value)
+
+
 EIG_STRIDE = 16
 EIG = dict(RCVR=0, INDEX=1, BOUNCES=2, THETA=3, PHI=4, TTIME=5, CELERITY=6, AMP_DB=7, ATTEN_DB=8, INCL=9, BEARING=10, BACKAZ=11,
            AZDEV=12, NSMP=13, SMP0=14)
@@ -772,6 +807,38 @@ class FanContext:
         st = np.zeros(4, dtype=np.uint64)
         self._chk(self.lib.geoac_fan_tubemap_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
         return dict(triangles=int(st[0]), cooperative=int(st[1]), candidates=int(st[2]))
+
+    # ---- level tube maps (include/geoac_ltubemap.h): the rasteriser runs on the device; nothing is computed here ----
+    def level_tubemap(self, spec=None, **kw):
+        """geoac_fan_level_tubemap of the last launch (one with set_levels): `spec` an LTubeSpec, or the arguments of ltube_spec().  Returns a dict of
+        numpy arrays: count, ttime_min, atten_min, first [M][Ls][n0][n1] and reach [Ls][n0][n1] (Ls: the levels level_mask selects, in ascending
+        level index).  May be called again with another spec without a new launch."""
+        if spec is None:
+            spec = ltube_spec(**kw)
+        self._chk(self.lib.geoac_fan_level_tubemap(self._h, ctypes.byref(spec)))
+        M, Ls, n0, n1 = (ctypes.c_int(0) for _ in range(4))
+        self._chk(self.lib.geoac_fan_level_tubemap_shape(self._h, *[ctypes.byref(v) for v in (M, Ls, n0, n1)]))
+        M, Ls, n0, n1 = M.value, Ls.value, n0.value, n1.value
+        out = {}
+        for name, layer, dtype in _LTUBE_LAYERS:
+            out[name] = np.empty((M, Ls, n0, n1), dtype=dtype)
+            self._chk(self.lib.geoac_fan_level_tubemap_fetch(self._h, layer, out[name].ctypes.data_as(ctypes.c_void_p)))
+        out["reach"] = np.empty((Ls, n0, n1), dtype=np.uint32)
+        self._chk(self.lib.geoac_fan_level_tubemap_fetch_reach(self._h, out["reach"].ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def level_tubemap_timing(self):
+        """HIP-event time of the last level_tubemap() on the context's stream [ms]"""
+        ms = ctypes.c_double(0)
+        self._chk(self.lib.geoac_fan_level_tubemap_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def level_tubemap_stats(self):
+        """work counters of the last level_tubemap(): triangles that proposed cell centres, those walked cooperatively by a wave, centres tested,
+        and whether the call formed the branch table (False: it found the one a former call or level_stations() had formed)"""
+        st = np.zeros(4, dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_level_tubemap_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
+        return dict(triangles=int(st[0]), cooperative=int(st[1]), candidates=int(st[2]), table_formed=bool(st[3]))
 
     def set_angles(self, theta_deg, phi_deg):
         th, ph = _arr(theta_deg), _arr(phi_deg)

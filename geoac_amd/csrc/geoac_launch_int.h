@@ -3,7 +3,7 @@
 // context and with the HIP runtime: device buffers that grow, the status of a failed HIP call, grid sizes, the event pair behind a *_timing
 // function, and the first steps of every entry point that reads the last completed launch.  Plain functions; each file keeps its own state and
 // its own entry points.  (What a pair of files alone shares has a header of its own: geoac_lattice_list.h for the two list searches, geoac_stations.hip
-// and geoac_lstations.hip, and geoac_newton_rounds.h for the two refinements, geoac_refine.hip and geoac_level_refine.hip.)
+// and geoac_lstations.hip, geoac_tube_walk.h for the two tube maps, geoac_tubemap.hip and geoac_ltubemap.hip, and geoac_newton_rounds.h for the two refinements, geoac_refine.hip and geoac_level_refine.hip.)
 #ifndef GEOAC_LAUNCH_INT_H_
 #define GEOAC_LAUNCH_INT_H_
 

@@ -10,7 +10,8 @@
 //                  crossings once, in path order, with two ordinal counters (upward, downward) that reset when the leg changes, and files
 //                  crossing k under its branch b = ((leg - leg0) * 2 + d) * ord_max + o.  The table is cleared first: an absent branch
 //                  reads present = 0.  The ray index is the fastest axis, so the corner loads of neighbouring lanes coalesce as they do on
-//                  the landing table of k_sta_count.  It depends on the launch, leg0, n_legs and ord_max, and is kept while those hold.
+//                  the landing table of k_sta_count.  It depends on the launch, leg0, n_legs and ord_max, and is kept while those hold
+//                  (geoac_lsta_xland_dev, which geoac_ltubemap.hip calls too: one table serves the lists and the level tube map).
 //   k_lsta_count, k_lsta_rows    the two passes of geoac_lattice_list.h over the list segments (member, station, branch, chunk of lattice
 //                  cells): a plane is (m, level_of[s], b) of the table, the rows come out sorted by b * n_tri + tri.  What is this file's
 //                  own is LstaDev below: which plane, no filter, and a row that reads the three corners' crossing records through slot k.
@@ -186,6 +187,53 @@ extern "C" void geoac_lsta_release(void* state){
     delete st;
 }
 
+// the branch table of the last completed launch under (leg_min, leg_max, ord_max): formed on first use after a launch or when the three give
+// another (leg0, n_legs, ord_max), and kept until then.  The level-station state is created if the context has none.
+extern "C" int geoac_lsta_xland_dev(geoac_ctx* ctx, const char* what, int leg_min, int leg_max, int ord_max, const void** xland_dev, int* n_branches, int* leg0,
+                                    int* n_legs, int* formed){
+    LBound b;
+    int rc = lbind(ctx, what, true, &b);
+    if(rc) return rc;
+    const GeoacMapView& v = b.v.map;
+    void* lrec = nullptr; void* lcount = nullptr; size_t lrec_bytes = 0, lcount_bytes = 0;
+    if((rc = geoac_fan_levels_dev(ctx, &lrec, &lrec_bytes, &lcount, &lcount_bytes)))
+        return geoac_map_fail(ctx, rc, (std::string(what) + ": " + geoac_last_error(ctx)).c_str());
+    int L = 0, capL = 0;
+    if((rc = geoac_get_levels(ctx, &L, nullptr, &capL))) return rc;
+    if(leg_min < 0 || leg_max < leg_min || ord_max < 1 || ord_max > GEOAC_LVL_MAX_CAP || L < 1 || capL < 1 ||
+       lrec_bytes != sizeof(double) * GEOAC_LVL_STRIDE * (size_t)v.M * v.n_rays * L * capL || lcount_bytes != sizeof(int) * (size_t)v.M * v.n_rays * L)
+        return geoac_map_fail(ctx, GEOAC_E_INVALID, (std::string(what) + ": the branch table needs 0 <= leg_min <= leg_max, ord_max in 1 .. 64 and crossing records of the launch's shape").c_str());
+    LstaState* st = b.st;
+    hipStream_t s = (hipStream_t)v.stream;
+    LstaDev D{};
+    D.lrec = (const double*)lrec; D.lcount = (const int*)lcount;
+    D.spherical = spherical(v.eqset) ? 1 : 0;
+    D.M = v.M; D.L = L; D.capL = capL; D.n_rays = v.n_rays;
+    int n_cells = 0;
+    geoac_lattice_extent(leg_min, leg_max, v.legs, 2, 2, 0, &D.leg0, &D.n_legs, &n_cells);       // (the legs do not depend on the lattice)
+    D.ord_max = ord_max;
+    D.n_planes = D.n_legs * 2 * D.ord_max;
+    const size_t n_xland = (size_t)v.M * L * D.n_planes * v.n_rays;
+    const bool form = n_xland > 0 && (st->xland_gen != v.gen || st->x_leg0 != D.leg0 || st->x_n_legs != D.n_legs || st->x_ord_max != D.ord_max);
+    if(form){
+        st->xland_gen = 0;
+        if(grow(&st->xland, &st->xland_cap, sizeof(double4) * n_xland))
+            return geoac_map_fail(ctx, GEOAC_E_NOMEM, (std::string(what) + ": no device memory for the branch table (" + std::to_string((sizeof(double4) * n_xland) >> 20) + " MiB)").c_str());
+        D.xland = (double4*)st->xland;
+        // cleared first: an absent branch reads present = 0
+        GEOAC_CHK(what, hipMemsetAsync(st->xland, 0, sizeof(double4) * n_xland, s));
+        hipLaunchKernelGGL(k_lsta_prep, dim3(blocks_for((long long)v.M * v.n_rays * L, 256)), dim3(256), 0, s, D);
+        GEOAC_CHK(what, hipGetLastError());
+        st->xland_gen = v.gen; st->x_leg0 = D.leg0; st->x_n_legs = D.n_legs; st->x_ord_max = D.ord_max;
+    }
+    if(xland_dev) *xland_dev = st->xland;
+    if(n_branches) *n_branches = D.n_planes;
+    if(leg0) *leg0 = D.leg0;
+    if(n_legs) *n_legs = D.n_legs;
+    if(formed) *formed = form ? 1 : 0;
+    return GEOAC_OK;
+}
+
 extern "C" const char* geoac_lstation_fault(int eqset, const geoac_lstation_spec* spec, int n_rays, int n_levels, int n_sta, const int32_t* level_of){
     int code;
     return lspec_fault(eqset, spec, n_rays, n_levels, n_sta, level_of, &code);
@@ -232,27 +280,15 @@ extern "C" int geoac_fan_level_stations(geoac_ctx* ctx, const geoac_lstation_spe
     geoac_lattice_extent(spec->leg_min, spec->leg_max, v.legs, nt, np, spec->phi_periodic, &D.leg0, &D.n_legs, &D.n_cells);
     D.ord_max = spec->ord_max;
     const long long n_seg_all = list_segments(&D, D.n_legs * 2 * D.ord_max);
-    const size_t n_xland = (size_t)v.M * L * D.n_planes * v.n_rays;
 
     const size_t n_axes = (size_t)nt + np + 2 * (size_t)n_sta;
     const size_t out_need = st->rows_bytes() + st->hits_bytes();
-    const bool form = n_xland > 0 && (st->xland_gen != v.gen || st->x_leg0 != D.leg0 || st->x_n_legs != D.n_legs || st->x_ord_max != D.ord_max);
-    if(form){
-        st->xland_gen = 0;
-        if(grow(&st->xland, &st->xland_cap, sizeof(double4) * n_xland))
-            return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_level_stations: no device memory for the branch table (" + std::to_string((sizeof(double4) * n_xland) >> 20) + " MiB)").c_str());
-    }
+    const void* xland = nullptr;
+    if((rc = geoac_lsta_xland_dev(ctx, what, spec->leg_min, spec->leg_max, spec->ord_max, &xland, nullptr, nullptr, nullptr, nullptr))) return rc;
     if(list_grow(&st->lb, D, sizeof(int32_t) * (size_t)n_sta, n_seg_all, out_need))
         return geoac_map_fail(ctx, GEOAC_E_NOMEM, ("fan_level_stations: no device memory for the lists (" + std::to_string(out_need >> 20) + " MiB for " + std::to_string(v.M) + " members x " +
                                                    std::to_string(n_sta) + " stations x " + std::to_string(spec->cap) + " rows)").c_str());
-    D.xland = (double4*)st->xland;
-    if(form){
-        // cleared first: an absent branch reads present = 0
-        GEOAC_CHK(what, hipMemsetAsync(st->xland, 0, sizeof(double4) * n_xland, s));
-        hipLaunchKernelGGL(k_lsta_prep, dim3(blocks_for((long long)v.M * v.n_rays * L, 256)), dim3(256), 0, s, D);
-        GEOAC_CHK(what, hipGetLastError());
-        st->xland_gen = v.gen; st->x_leg0 = D.leg0; st->x_n_legs = D.n_legs; st->x_ord_max = D.ord_max;
-    }
+    D.xland = (double4*)xland;
     // lattice axes and stations, and behind them the stations' levels: a second host block, a second copy (list_fill left the stream idle:
     // no earlier call's copy still reads the block)
     GEOAC_CHK(what, list_fill(&st->lb, &D, b.v, sta, s));

@@ -46,8 +46,9 @@
  * geoac_last_error names which of the two failed.  All device work goes to the context's stream.  A context that never calls an entry point of
  * this header allocates nothing and launches nothing for it.
  *
- * Not covered: the amplitude at altitude (path rows carry no Jacobian), a tube map at altitude, the pool (geoac_multi.h) and the command-line
- * drivers.  The estimates are refined by a call of their own: geoac_fan_level_refine (geoac_level_refine.h) takes every kept row of these lists
+ * Not covered: the amplitude at altitude (path rows carry no Jacobian), the pool (geoac_multi.h) and the command-line drivers.  A tube map at
+ * altitude - these hits at every cell centre of a grid, reduced - is geoac_fan_level_tubemap (geoac_ltubemap.h), which shares the branch table
+ * this call forms.  The estimates are refined by a call of their own: geoac_fan_level_refine (geoac_level_refine.h) takes every kept row of these lists
  * as a seed and iterates it to the ray that passes the station (geoac_fan_refine works on the ground lists).
  */
 #ifndef GEOAC_LSTATIONS_H_
