@@ -16,4 +16,5 @@ from .api import (  # noqa: F401
     LStationSpec, lstation_spec, lstation_check, LSTA, LSTA_STRIDE,
     LTubeSpec, ltube_spec, ltube_check, LTUBE,
     LevelRefineSpec, level_refine_spec, level_refine_check, LRF, LRF_STRIDE, LRF_STATUS,
+    level_amp_check, LAMP, LAMP_STRIDE, LAMP_STATUS,
 )

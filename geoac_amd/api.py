@@ -180,6 +180,20 @@ def level_refine_check(eqset, spec):
         raise GeoAcError(f"geoac_level_refine_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
 
 
+LAMP_STRIDE = 16
+LAMP = dict(MEMBER=0, INDEX=1, LEG=2, DIR=3, ORD=4, STATUS=5, THETA=6, PHI=7, DET=8, TZ=9, D=10, AMP=11, C=12, RHO=13, TTIME=14, ATTEN=15)
+LAMP_STATUS = dict(OK=1, ABSENT=2, NO_PROBE=3, SINGULAR=4, SKIPPED=5)
+
+
+def level_amp_check(eqset, probe_deg):
+    """geoac_level_amp_check: host-only validation (no GPU needed); raises GeoAcError naming the fault"""
+    lib = load_library()
+    fault = ctypes.c_char_p()
+    rc = lib.geoac_level_amp_check(int(eqset), ctypes.c_double(float(probe_deg)), ctypes.byref(fault))
+    if rc:
+        raise GeoAcError(f"geoac_level_amp_check: {lib.geoac_strerror(rc).decode()}: {fault.value.decode()}")
+
+
 class TubeSpec(ctypes.Structure):
     """geoac_tube_spec (include/geoac_tubemap.h): the grid of a MapSpec, the lattice and triangle filters of a StationSpec, the band on a hit's
     interpolated turning height and the detection threshold of a tube map"""
@@ -785,6 +799,39 @@ class FanContext:
     def level_refine_timing(self):
         """HIP-event times of the last level_refine() [ms]: its launches, its own kernels"""
         return self._rounds_timing(self.lib.geoac_fan_level_refine_timing)
+
+    # ---- level amplitudes (include/geoac_level_amp.h): the ray-tube amplitude at a level runs on the device; nothing is computed here ----
+    def _level_amp_rows(self):
+        n, M = ctypes.c_int(0), ctypes.c_int(0)
+        self._chk(self.lib.geoac_fan_level_amp_shape(self._h, ctypes.byref(n), ctypes.byref(M)))
+        rows = np.empty((n.value, LAMP_STRIDE))
+        self._chk(self.lib.geoac_fan_level_amp_fetch(self._h, _p(rows)))
+        return rows, M.value
+
+    def level_amp_at(self, theta_deg, phi_deg, level_of, leg, dir, ord, probe_deg=0.02):
+        """geoac_fan_level_amp_at: the tube amplitude of ray i at launch angles (theta_deg[i], phi_deg[i]) on level level_of[i] of the level list, branch
+        (leg[i], dir[i] = +1 up / -1 down, ord[i]); scalars serve every ray.  Launches one fan of 3 n rays (the rays and their two probes at + probe_deg)
+        with the level list still set, so the context's launch angles and last launch become that fan (n_rays = 3 n).  Returns rows [M][n][LAMP_STRIDE]
+        (columns LAMP, status values LAMP_STATUS), M = n_sources * n_members."""
+        th, ph = _arr(theta_deg).reshape(-1), _arr(phi_deg).reshape(-1)
+        n = len(th)
+        if len(ph) != n:
+            raise GeoAcError("level_amp_at: theta_deg and phi_deg differ in length")
+        ints = [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.int32).reshape(-1), (n,))) for v in (level_of, leg, dir, ord)]
+        self._chk(self.lib.geoac_fan_level_amp_at(self._h, n, _p(th), _p(ph), *[v.ctypes.data_as(ctypes.c_void_p) for v in ints], ctypes.c_double(float(probe_deg))))
+        self.n_rays = 3 * n
+        rows, M = self._level_amp_rows()
+        return rows.reshape(M, n, LAMP_STRIDE)
+
+    def level_amp(self):
+        """geoac_fan_level_amp: the tube amplitude of every seed of the current level_refine() result, read from its final launch's crossing tables at its
+        probe_deg - no launch is made.  Returns rows [n_seeds][LAMP_STRIDE]; seeds that did not converge are SKIPPED."""
+        self._chk(self.lib.geoac_fan_level_amp(self._h))
+        return self._level_amp_rows()[0]
+
+    def level_amp_timing(self):
+        """HIP-event times of the last level_amp_at() / level_amp() [ms]: its launch (0 for level_amp()), its own kernels with the medium probe"""
+        return self._rounds_timing(self.lib.geoac_fan_level_amp_timing)
 
     # ---- tube maps (include/geoac_tubemap.h): the rasteriser runs on the device; nothing is computed here ----
     def tubemap(self, spec=None, **kw):

@@ -28,6 +28,7 @@
 #include "geoac_lstations_int.h"
 #include "geoac_ltubemap_int.h"
 #include "geoac_level_refine_int.h"
+#include "geoac_level_amp_int.h"
 #include "geoac_levels_int.h"
 
 extern "C" void geoac_natural_spline_slopes(int n, const double* x, const double* f, double* slopes);
@@ -258,6 +259,8 @@ struct geoac_ctx {
     std::vector<double> rfn_mem;                  // [M][GEOAC_RFN_MEMW] of the last geoac_rfn_view
     void* lrf_state = nullptr;                    // level refinement (geoac_level_refine.hip): NULL until the first geoac_fan_level_refine
     std::vector<double> lrf_src;                  // [M][2] of the last geoac_lrf_view
+    void* lamp_state = nullptr;                   // level amplitudes (geoac_level_amp.hip): NULL until the first geoac_fan_level_amp_at / geoac_fan_level_amp
+    std::vector<double> lamp_src;                 // [M][3] of the last geoac_lamp_view
     std::vector<double> ens_u, ens_v;             // every member's winds on the host (K > 1), beside ens_T: the Mach numbers at the source the refinement needs
     std::string err;
 };
@@ -560,6 +563,7 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->ltube_state){ geoac_ltube_release(ctx->ltube_state); ctx->ltube_state = nullptr; }
     if(ctx->rfn_state){ geoac_rfn_release(ctx->rfn_state); ctx->rfn_state = nullptr; }
     if(ctx->lrf_state){ geoac_lrf_release(ctx->lrf_state); ctx->lrf_state = nullptr; }
+    if(ctx->lamp_state){ geoac_lamp_release(ctx->lamp_state); ctx->lamp_state = nullptr; }
     DevBuf* bufs[] = { &ctx->d_mconsts, &ctx->seg, &ctx->rhot, &ctx->theta, &ctx->phi, &ctx->state, &ctx->rec, &ctx->counters, &ctx->perm,
                        &ctx->path[0], &ctx->path[1], &ctx->path[2], &ctx->contrib[0], &ctx->contrib[1], &ctx->contrib[2],
                        &ctx->ev_row[0], &ctx->ev_row[1], &ctx->ev_row[2], &ctx->ev_m[0], &ctx->ev_m[1], &ctx->ev_m[2],
@@ -1993,6 +1997,28 @@ int geoac_lrf_view(geoac_ctx* ctx, GeoacLrfView* v){
     v->n_members = M; v->src = ctx->lrf_src.data();
     v->r_earth = ctx->prm.r_earth; v->mode = ctx->prm.mode;
     v->state = &ctx->lrf_state;
+    return GEOAC_OK;
+}
+
+// ... and geoac_level_amp.hip (geoac_level_amp_int.h): the same view, the members' source points as the parameters hold them, and the parameter block
+// of the last completed launch for the probe launchers
+int geoac_lamp_view(geoac_ctx* ctx, GeoacLampView* v){
+    int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
+    if(rc) return rc;
+    const int K = ctx->n_members, M = ctx->n_src * K;
+    ctx->lamp_src.assign((size_t)M * 3, 0.0);
+    // the source point, z_grnd and r_earth are those the rays of the last completed launch were launched with (its parameter block), not the
+    // parameters now: geoac_set_params does not end a result.  (geoac_set_sources does: the source list is the launch's while a result is current.)
+    const bool ran = ctx->ran;
+    for(int m = 0; m < M; m++){
+        const double* src = ctx->n_src > 1 ? &ctx->sources[(size_t)(m / K) * 3] : (ran ? ctx->lastP.src : ctx->prm.src);
+        for(int q = 0; q < 3; q++) ctx->lamp_src[(size_t)m * 3 + q] = src[q];
+    }
+    v->n_members = M; v->n_profiles = K; v->grid = ctx->have_grid ? 1 : 0; v->src3 = ctx->lamp_src.data();
+    v->r_earth = (ran && ctx->lastP.r_earth != 0.0) ? ctx->lastP.r_earth : ctx->prm.r_earth;          // (the block holds 0 on the Cartesian sets, which do not use it)
+    v->z_grnd = ran ? ctx->lastP.z_grnd : ctx->prm.z_grnd; v->mode = ctx->prm.mode;
+    v->dev_params = ctx->ran ? &ctx->lastP : nullptr;
+    v->state = &ctx->lamp_state;
     return GEOAC_OK;
 }
 

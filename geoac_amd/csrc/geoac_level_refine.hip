@@ -332,3 +332,18 @@ extern "C" int geoac_fan_level_refine_stats(geoac_ctx* ctx, uint64_t stats[6]){
     int rc = bind_result(ctx, "fan_level_refine_stats", &b);
     return rc ? rc : rounds_stats(ctx, "fan_level_refine_stats", *b.st, stats);
 }
+
+// (geoac_level_refine_int.h: for geoac_level_amp.hip)
+extern "C" int geoac_lrf_seeds(geoac_ctx* ctx, const char* what, GeoacLrfSeeds* out){
+    Bound b;
+    int rc = bind_result(ctx, what, &b);
+    if(rc) return rc;
+    const LrfDev& D = b.st->h;
+    const long long N = b.st->n_seeds;
+    *out = GeoacLrfSeeds{};
+    out->n_seeds = b.st->n_seeds;
+    if(N == 0) return GEOAC_OK;                                   // (no block was carved: h is the last call's)
+    out->M = D.M; out->L = D.L; out->capL = D.capL; out->probe_deg = D.h;
+    out->meta = D.meta; out->status = D.state; out->theta = D.best; out->phi = D.best + N;
+    return GEOAC_OK;
+}

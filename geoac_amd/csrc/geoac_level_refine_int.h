@@ -19,4 +19,17 @@ struct GeoacLrfView {
 extern "C" int  geoac_lrf_view(geoac_ctx* ctx, GeoacLrfView* v);
 extern "C" void geoac_lrf_release(void* state);                                  // geoac_destroy: frees the refinement state (device current, stream idle)
 
+// what geoac_level_amp.hip reads of a current refinement result: the seeds' device arrays in the refinement's own block (valid until the next
+// geoac_fan_level_refine) and the shape of its final launch, whose crossing tables geoac_fan_levels_dev still holds.  GEOAC_E_INVALID (with the
+// message of the *_fetch calls, `what` in front) when there is no current result.
+struct GeoacLrfSeeds {
+    int n_seeds, M, L, capL;
+    double probe_deg;
+    const int* meta;               // [n_seeds][6]: member, station, level, leg, direction (0 up, 1 down), ordinal
+    const int* status;             // [n_seeds]: GEOAC_RFN_CONVERGED ..
+    const double* theta;           // [n_seeds]: the best point, = the base ray's launch angles in the final launch
+    const double* phi;
+};
+extern "C" int  geoac_lrf_seeds(geoac_ctx* ctx, const char* what, GeoacLrfSeeds* out);
+
 #endif
