@@ -15,6 +15,7 @@ from .api import (  # noqa: F401
     levels_check, LVL, LVL_STRIDE, MAX_LEVELS,
     LStationSpec, lstation_spec, lstation_check, LSTA, LSTA_STRIDE,
     LTubeSpec, ltube_spec, ltube_check, LTUBE,
+    LAmpMapSpec, lampmap_spec, lampmap_check, LAMPMAP,
     LevelRefineSpec, level_refine_spec, level_refine_check, LRF, LRF_STRIDE, LRF_STATUS,
     level_amp_check, LAMP, LAMP_STRIDE, LAMP_STATUS,
 )

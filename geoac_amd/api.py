@@ -264,6 +264,38 @@ def ltube_check(eqset, spec, n_rays, n_levels):
     return int(cells.value), int(n_sel.value)
 
 
+class LAmpMapSpec(ctypes.Structure):
+    """geoac_lampmap_spec (include/geoac_lampmap.h): the fields of an LTubeSpec, then det_floor and detect_amp"""
+    _fields_ = LTubeSpec._fields_ + [("det_floor", ctypes.c_double), ("detect_amp", ctypes.c_double)]
+
+
+LAMPMAP = dict(COUNT=0, WEAK=1, AMP_MAX=2, RAMP_MAX=3, LOUDEST=4)
+_LAMPMAP_LAYERS = (("count", LAMPMAP["COUNT"], np.uint64), ("weak", LAMPMAP["WEAK"], np.uint64), ("amp_max", LAMPMAP["AMP_MAX"], np.float64),
+                   ("ramp_max", LAMPMAP["RAMP_MAX"], np.float64), ("loudest", LAMPMAP["LOUDEST"], np.int64))
+
+
+def lampmap_spec(origin, step, n, n_theta, n_phi, edge_max, level_mask, wrap_lon=False, phi_periodic=False, leg_min=0, leg_max=2**31 - 1, ord_max=1,
+                 dir_mask=3, det_floor=0.0, detect_amp=float("nan")):
+    """an LAmpMapSpec from plain values: the arguments of ltube_spec(), the smallest |DET| a hit may have to carry an amplitude, and the received
+    amplitude from which a member counts in the DETECT layer (NaN: no such layer)"""
+    return LAmpMapSpec((ctypes.c_double * 2)(*[float(v) for v in origin]), (ctypes.c_double * 2)(*[float(v) for v in step]), (ctypes.c_int * 2)(*[int(v) for v in n]),
+                       1 if wrap_lon else 0, int(n_theta), int(n_phi), 1 if phi_periodic else 0, int(leg_min), int(leg_max), int(ord_max), float(edge_max),
+                       int(dir_mask), int(level_mask), float(det_floor), float(detect_amp))
+
+
+def lampmap_check(eqset, spec, n_rays, n_levels):
+    """geoac_lampmap_check: host-only validation (no GPU needed) against a launch of n_rays rays and n_levels levels; returns the cell count and the
+    number of selected levels, or raises GeoAcError naming the first fault"""
+    lib = load_library()
+    lib.geoac_lampmap_fault.restype = ctypes.c_char_p
+    cells, n_sel = ctypes.c_int64(0), ctypes.c_int(0)
+    rc = lib.geoac_lampmap_check(int(eqset), ctypes.byref(spec), int(n_rays), int(n_levels), ctypes.byref(cells), ctypes.byref(n_sel))
+    if rc:
+        fault = lib.geoac_lampmap_fault(int(eqset), ctypes.byref(spec), int(n_rays), int(n_levels))
+        raise GeoAcError(f"geoac_lampmap_check: {lib.geoac_strerror(rc).decode()}: {fault.decode()}")
+    return int(cells.value), int(n_sel.value)
+
+
 EIG_STRIDE = 16
 EIG = dict(RCVR=0, INDEX=1, BOUNCES=2, THETA=3, PHI=4, TTIME=5, CELERITY=6, AMP_DB=7, ATTEN_DB=8, INCL=9, BEARING=10, BACKAZ=11,
            AZDEV=12, NSMP=13, SMP0=14)
@@ -885,6 +917,39 @@ class FanContext:
         and whether the call formed the branch table (False: it found the one a former call or level_stations() had formed)"""
         st = np.zeros(4, dtype=np.uint64)
         self._chk(self.lib.geoac_fan_level_tubemap_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
+        return dict(triangles=int(st[0]), cooperative=int(st[1]), candidates=int(st[2]), table_formed=bool(st[3]))
+
+    # ---- level loudness maps (include/geoac_lampmap.h): the rasteriser and the amplitude chain run on the device; nothing is computed here ----
+    def level_ampmap(self, spec=None, **kw):
+        """geoac_fan_level_ampmap of the last launch (one with set_levels): `spec` an LAmpMapSpec, or the arguments of lampmap_spec().  Returns a dict
+        of numpy arrays: count, weak, amp_max, ramp_max, loudest [M][Ls][n0][n1] and detect [Ls][n0][n1] (None when detect_amp is NaN).  May be
+        called again with another spec without a new launch."""
+        if spec is None:
+            spec = lampmap_spec(**kw)
+        self._chk(self.lib.geoac_fan_level_ampmap(self._h, ctypes.byref(spec)))
+        M, Ls, n0, n1, det = (ctypes.c_int(0) for _ in range(5))
+        self._chk(self.lib.geoac_fan_level_ampmap_shape(self._h, *[ctypes.byref(v) for v in (M, Ls, n0, n1, det)]))
+        M, Ls, n0, n1 = M.value, Ls.value, n0.value, n1.value
+        out = {}
+        for name, layer, dtype in _LAMPMAP_LAYERS:
+            out[name] = np.empty((M, Ls, n0, n1), dtype=dtype)
+            self._chk(self.lib.geoac_fan_level_ampmap_fetch(self._h, layer, out[name].ctypes.data_as(ctypes.c_void_p)))
+        out["detect"] = None
+        if det.value:
+            out["detect"] = np.empty((Ls, n0, n1), dtype=np.uint32)
+            self._chk(self.lib.geoac_fan_level_ampmap_fetch_detect(self._h, out["detect"].ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def level_ampmap_timing(self):
+        """HIP-event time of the last level_ampmap() on the context's stream [ms]"""
+        ms = ctypes.c_double(0)
+        self._chk(self.lib.geoac_fan_level_ampmap_timing(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def level_ampmap_stats(self):
+        """work counters of the last level_ampmap(), as level_tubemap_stats() gives them"""
+        st = np.zeros(4, dtype=np.uint64)
+        self._chk(self.lib.geoac_fan_level_ampmap_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
         return dict(triangles=int(st[0]), cooperative=int(st[1]), candidates=int(st[2]), table_formed=bool(st[3]))
 
     def set_angles(self, theta_deg, phi_deg):

@@ -27,6 +27,7 @@
 #include "geoac_refine_int.h"
 #include "geoac_lstations_int.h"
 #include "geoac_ltubemap_int.h"
+#include "geoac_lampmap_int.h"
 #include "geoac_level_refine_int.h"
 #include "geoac_level_amp_int.h"
 #include "geoac_levels_int.h"
@@ -256,6 +257,7 @@ struct geoac_ctx {
     void* rfn_state = nullptr;                    // station refinement (geoac_refine.hip): NULL until the first geoac_fan_refine
     void* lsta_state = nullptr;                   // level stations (geoac_lstations.hip): NULL until the first geoac_fan_level_stations
     void* ltube_state = nullptr;                  // level tube maps (geoac_ltubemap.hip): NULL until the first geoac_fan_level_tubemap
+    void* lampmap_state = nullptr;                // level loudness maps (geoac_lampmap.hip): NULL until the first geoac_fan_level_ampmap
     std::vector<double> rfn_mem;                  // [M][GEOAC_RFN_MEMW] of the last geoac_rfn_view
     void* lrf_state = nullptr;                    // level refinement (geoac_level_refine.hip): NULL until the first geoac_fan_level_refine
     std::vector<double> lrf_src;                  // [M][2] of the last geoac_lrf_view
@@ -561,6 +563,7 @@ int geoac_destroy(geoac_ctx* ctx){
     if(ctx->tube_state){ geoac_tube_release(ctx->tube_state); ctx->tube_state = nullptr; }
     if(ctx->lsta_state){ geoac_lsta_release(ctx->lsta_state); ctx->lsta_state = nullptr; }
     if(ctx->ltube_state){ geoac_ltube_release(ctx->ltube_state); ctx->ltube_state = nullptr; }
+    if(ctx->lampmap_state){ geoac_lampmap_release(ctx->lampmap_state); ctx->lampmap_state = nullptr; }
     if(ctx->rfn_state){ geoac_rfn_release(ctx->rfn_state); ctx->rfn_state = nullptr; }
     if(ctx->lrf_state){ geoac_lrf_release(ctx->lrf_state); ctx->lrf_state = nullptr; }
     if(ctx->lamp_state){ geoac_lamp_release(ctx->lamp_state); ctx->lamp_state = nullptr; }
@@ -1941,7 +1944,7 @@ int geoac_launch_view(geoac_ctx* ctx, int slot, GeoacLaunchView* v){
     int rc = geoac_map_view(ctx, v ? &v->map : nullptr);
     if(rc) return rc;
     v->theta_deg = ctx->ang_th.data(); v->phi_deg = ctx->ang_ph.data(); v->n_ang = (int)ctx->ang_th.size();
-    v->state = slot == GEOAC_SLOT_STA ? &ctx->sta_state : (slot == GEOAC_SLOT_TUBE ? &ctx->tube_state : (slot == GEOAC_SLOT_LSTA ? &ctx->lsta_state : (slot == GEOAC_SLOT_LTUBE ? &ctx->ltube_state : &ctx->map_state)));
+    v->state = slot == GEOAC_SLOT_STA ? &ctx->sta_state : (slot == GEOAC_SLOT_TUBE ? &ctx->tube_state : (slot == GEOAC_SLOT_LSTA ? &ctx->lsta_state : (slot == GEOAC_SLOT_LTUBE ? &ctx->ltube_state : (slot == GEOAC_SLOT_LAMPMAP ? &ctx->lampmap_state : &ctx->map_state))));
     return GEOAC_OK;
 }
 

@@ -32,6 +32,7 @@
 #include "geoac_level_refine_int.h"
 #include "geoac_level_amp_int.h"
 #include "geoac_newton_rounds.h"                  // (Carve; the series of geoac_rfn_series.h come with it)
+#include "geoac_lamp_tube.h"                      // (steps 3 to 5, shared with geoac_lampmap.hip)
 
 #pragma clang fp contract(off)
 
@@ -125,7 +126,6 @@ __global__ void __launch_bounds__(64) k_lamp_gather(const LampDev* __restrict__ 
     }
 }
 
-struct LampMedium { double c, u, v, rho; };
 // the probe's values at point p (< R + M)
 __device__ inline LampMedium lamp_medium(const LampDev& D, long long p){
     LampMedium m;
@@ -161,53 +161,8 @@ __global__ void __launch_bounds__(64) k_lamp_rows(const LampDev* __restrict__ Dp
             else { a10 = (ct1 - c1) / h; a11 = (cp1 - c1) / h; }
             det = a00 * a11 - a01 * a10;
             const LampMedium m = lamp_medium(D, t), s = lamp_medium(D, D.R + me[0]);      // member me[0] < M
-            double sth, cth, sph, cph;
-            rfn_sincosd(th, &sth, &cth); rfn_sincosd(ph, &sph, &cph);
-            const double n0 = Q[GEOAC_LVL_P0 + 3], n1 = Q[GEOAC_LVL_P0 + 4], n2 = Q[GEOAC_LVL_P0 + 5];
-            const double c3 = m.c * m.c * m.c, cs3 = s.c * s.c * s.c;
-            double nu, nu_s, G, Qm;
-            if(D.eqset == GEOAC_EQ_3D){
-                const double e0 = cth * sph, e1 = cth * cph;
-                const double MS = 1.0 + (e0 * (s.u / s.c) + e1 * (s.v / s.c));
-                const double nx = e0 / MS, ny = e1 / MS, nz = n0;
-                nu = (s.c - nx * m.u - ny * m.v) / m.c;
-                nu_s = 1.0 - (nx * s.u - ny * s.v) / s.c;
-                const double g0 = m.c * nx / nu + m.u, g1 = m.c * ny / nu + m.v, g2 = m.c * nz / nu;
-                G = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
-                tz = g2 / G;
-                const double q0 = s.c * nx / nu_s + s.u, q1 = s.c * ny / nu_s + s.v, qx = nx / nu_s, qy = ny / nu_s;
-                const double q2 = s.c * sqrt(1.0 - qx * qx - qy * qy);
-                Qm = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
-            } else if(D.eqset == GEOAC_EQ_3D_RNGDEP){
-                const double nm = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
-                const double j0 = m.c * n0 / nm + m.u, j1 = m.c * n1 / nm + m.v, j2 = m.c * n2 / nm;
-                const double J = sqrt(j0 * j0 + j1 * j1 + j2 * j2);
-                tz = j2 / J;
-                nu = (s.c - n0 * m.u - n1 * m.v) / m.c;
-                nu_s = 1.0 - n0 * s.u / s.c - n1 * s.v / s.c;
-                const double g0 = m.c * n0 / nu + m.u, g1 = m.c * n1 / nu + m.v, g2 = m.c * n2 / nu;
-                G = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
-                const double q0 = s.c * cth * sph + s.u, q1 = s.c * cth * cph + s.v, q2 = s.c * sth;
-                Qm = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
-            } else {
-                const double nm = sqrt(n0 * n0 + n1 * n1 + n2 * n2);
-                const double j0 = m.c * n0 / nm, j1 = m.c * n1 / nm + m.v, j2 = m.c * n2 / nm + m.u;
-                const double J = sqrt(j0 * j0 + j1 * j1 + j2 * j2);
-                tz = j0 / J;
-                const double e1 = cth * cph, e2 = cth * sph;
-                const double MS = 1.0 + (e1 * (s.v / s.c) + e2 * (s.u / s.c));
-                nu_s = 1.0 / MS;
-                nu = (s.c - n1 * m.v - n2 * m.u) / m.c;
-                const double g0 = m.c * n0 / nu, g1 = m.c * n1 / nu + m.v, g2 = m.c * n2 / nu + m.u;
-                G = sqrt(g0 * g0 + g1 * g1 + g2 * g2);
-                const double q0 = s.c * sth / nu_s, q1 = s.c * e1 / nu + s.v, q2 = s.c * e2 / nu + s.u;
-                Qm = sqrt(q0 * q0 + q1 * q1 + q2 * q2);
-            }
-            if(D.spherical){ const double r = D.r_level[me[2]]; dd = r * r * rfn_cos(c0 * kRfnPi / 180.0) * fabs(tz * det); }   // level me[2] < L <= GEOAC_MAX_LEVELS
-            else dd = fabs(tz * det) * (180.0 / kRfnPi) * (180.0 / kRfnPi);
-            const double num = m.rho * nu * c3 * Qm * cth;
-            const double den = s.rho * nu_s * cs3 * G * dd;
-            amp = 1.0 / (4.0 * kRfnPi) * sqrt(fabs(num / den));
+            // steps 3 to 5 (geoac_lamp_tube.h); level me[2] < L <= GEOAC_MAX_LEVELS
+            lamp_tube(D.eqset, m, s, th, ph, Q[GEOAC_LVL_P0 + 3], Q[GEOAC_LVL_P0 + 4], Q[GEOAC_LVL_P0 + 5], det, c0, D.r_level[me[2]], &tz, &dd, &amp);
             if(det == 0.0 || !rfn_finite(det) || dd == 0.0 || !rfn_finite(dd) || amp == 0.0 || !rfn_finite(amp)){
                 status = GEOAC_LAMP_SINGULAR;
                 det = 0.0; tz = 0.0; dd = 0.0; amp = 0.0;

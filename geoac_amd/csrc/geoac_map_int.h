@@ -23,8 +23,8 @@ struct GeoacMapView {
 };
 
 // the same view, the caller's launch angles as the context keeps them on the host (ray order, not the slot order of the device arrays), and
-// the pointer slot of the file that asked: arrival maps, station arrivals, tube maps, level stations or level tube maps
-enum { GEOAC_SLOT_MAP = 0, GEOAC_SLOT_STA = 1, GEOAC_SLOT_TUBE = 2, GEOAC_SLOT_LSTA = 3, GEOAC_SLOT_LTUBE = 4 };
+// the pointer slot of the file that asked: arrival maps, station arrivals, tube maps, level stations, level tube maps or level loudness maps
+enum { GEOAC_SLOT_MAP = 0, GEOAC_SLOT_STA = 1, GEOAC_SLOT_TUBE = 2, GEOAC_SLOT_LSTA = 3, GEOAC_SLOT_LTUBE = 4, GEOAC_SLOT_LAMPMAP = 5 };
 struct GeoacLaunchView {
     GeoacMapView map;              // (its `state` is always the map's slot)
     const double* theta_deg;       // [n_ang] host, the angles of geoac_fan_set_angles

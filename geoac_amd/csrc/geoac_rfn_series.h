@@ -54,6 +54,21 @@ __device__ inline double rfn_dist(double lat1, double lon1, double lat2, double 
 }
 __device__ inline bool rfn_finite(double v){ return v - v == 0.0; }
 
+// EXP of include/geoac_lampmap.h, which is normative for it (restated in tests/lampmap_reference.py): reduction by multiples of ln 2 with a split
+// constant (q * kRfnLn2Hi is exact: 31 significant bits times at most 11), a Horner sum of 14 Taylor terms on |r| <= 0.347, and an exact power of two.
+// Below -700 it returns 0.0, so that no result is subnormal (exp(-700) = 9.8e-305); above 700 +inf.
+const double kRfnLn2 = 0.693147180559945309417, kRfnLn2Hi = 6.93147180369123816490e-01, kRfnLn2Lo = 1.90821492927058770002e-10;
+__device__ inline double rfn_exp(double x){
+    if(x != x) return x;
+    if(x < -700.0) return 0.0;
+    if(x > 700.0) return (double)INFINITY;
+    const double q = floor(x / kRfnLn2 + 0.5);                  // |q| <= 1010
+    const double r = (x - q * kRfnLn2Hi) - q * kRfnLn2Lo;
+    double s = 1.0;
+    for(int k = 14; k >= 1; k--) s = 1.0 + (r * s) / (double)k;
+    return s * __longlong_as_double((long long)((int)q + 1023) << 52);          // biased exponent 13 .. 2033: a normal power of two
+}
+
 }  // namespace
 
 #endif

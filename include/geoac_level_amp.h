@@ -80,8 +80,8 @@
  * stream; a context that never calls an entry point of this header allocates nothing and launches nothing for it.
  *
  * Not covered: ensembles with K > 1 (they need a member view of the probe evaluators); GEOAC_EQ_GLOBAL_RNGDEP (it needs a convergence test of the
- * tube in probe_deg, a second pair of probes, and a status for its failure); an amplitude layer of the level tube maps; amplitudes of a
- * whole lattice fan; the pool and the command-line drivers; the 2-D set.
+ * tube in probe_deg, a second pair of probes, and a status for its failure); the pool and the command-line drivers; the 2-D set.  (A first-order
+ * amplitude of a whole lattice fan per map cell, for ensembles too, is geoac_lampmap.h's.)
  */
 #ifndef GEOAC_LEVEL_AMP_H_
 #define GEOAC_LEVEL_AMP_H_

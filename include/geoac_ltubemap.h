@@ -35,8 +35,8 @@
  * on the order-preserving 64-bit key of the double (geoac_map.h), and every reduction is an integer atomic: a map is the same bits on every run.
  *
  * There is no celerity layer.  A celerity at altitude is a range over a time, and the range needs each member's source point and the range
- * series of geoac_level_refine.h; a caller has both the cell centre and TTIME_MIN and forms it with its own source.  There is no amplitude:
- * path rows carry no Jacobian (geoac_levels.h).
+ * series of geoac_level_refine.h; a caller has both the cell centre and TTIME_MIN and forms it with its own source.  There is no amplitude
+ * layer here: path rows carry no Jacobian (geoac_levels.h).  geoac_fan_level_ampmap (geoac_lampmap.h) forms one from the crossing triangles themselves.
  *
  * Refusals (geoac_ltube_fault names the first).  GEOAC_EQ_2D: GEOAC_E_UNSUPPORTED.  GEOAC_E_INVALID: everything geoac_map_check refuses for
  * origin, step, n and wrap_lon, everything geoac_lstation_check refuses for n_theta, n_phi, phi_periodic, leg_min, leg_max,
